@@ -15,6 +15,13 @@ alleles (2.5e7 per GPU: K2 record prep + K3 grouped dedup + K4 long-key digests)
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c2|c3|c5]
     torchrun --nproc-per-node N bench.py --gpus N ...
+
+A plain run sets up, warms up, times the K steps and prints the result line (value,
+``ms_per_step``).  ``--full`` adds what takes runs of its own: the CPU baselines, the
+keyed C4k step attached to the default line as ``keyed``, the per-stage event pass
+(``config.stage_ms``) and the roofline accounting.  ``--dump-outputs DIR`` writes what
+the last timed step computed as ``DIR/<name>.npy`` (same arguments, same inputs: two
+builds can be compared array by array).
 """
 
 from __future__ import annotations
@@ -93,11 +100,69 @@ def stream_ceiling(test: str, pmc_path: str, kernel_ms: float):
                       "(tools/hbm_ceiling.hip, 16-B grid-stride streams, read:write 1:3, best access form)"}
 
 
+DUMP_BYTES = 48 << 20  # --dump-outputs: all arrays of one dump together stay under 64 MB
+
+
+def dump_outputs(dirname: str, arrays: dict) -> None:
+    """--dump-outputs: ``arrays`` (name -> tensor) as ``dirname/<name>.npy``, 8/16-bit
+    integers as float32 and wider ones as float64 (both exact).  Each array has an equal
+    share of DUMP_BYTES; a larger one is written as a fixed sample of its rows (sorted
+    indices from numpy PCG64, seed 1234: the same rows for arrays of the same length)."""
+    os.makedirs(dirname, exist_ok=True)
+    share = DUMP_BYTES // max(1, len(arrays))
+    for nm, t in arrays.items():
+        wide = t.element_size() > 2
+        rows = t.shape[0]
+        row_bytes = int(np.prod(t.shape[1:], dtype=np.int64)) * (8 if wide else 4)
+        if rows * row_bytes > share:
+            idx = np.sort(np.random.default_rng(1234).integers(0, rows, share // row_bytes))
+            t = t[torch.from_numpy(idx).to(t.device)]
+        np.save(os.path.join(dirname, nm + ".npy"), t.cpu().numpy().astype(np.float64 if wide else np.float32))
+
+
+def step_outputs(name, n, code, hist, ctr, keyed, last) -> dict:
+    """What a caller of the timed step holds after the last one (device tensors by name).
+    ``keyed``: the KeyedStep / PrepStep of the record workloads.  The L8 histogram and the
+    counters are the sums over the timed steps.  Only specified bytes: the key / path text up
+    to its end, the digest rows of the long records."""
+    arrs = {"l8_histogram": hist, "counters": ctr}
+    if name in ("c2", "c3", "c4"):
+        arrs["code"] = code
+    elif keyed is not None:
+        o = keyed.out
+        arrs.update(end=o["end"], code=o["code"], status=o["status"], keep=o["keep"][:n])
+        if o["digest"] is not None:
+            arrs.update(is_long=o["is_long"], digest_long=o["digest"][o["is_long"] != 0])
+        kt = o.get("kt")
+        if kt is not None:
+            ko, po = kt.key_offsets(n), kt.path_offsets(n)
+            arrs.update(key_off=ko, path_off=po, key_state=kt.state[:n], keys=kt.keys[:int(ko[n].item())],
+                        paths=kt.paths[:int(po[n].item())])
+    elif name == "vcf":
+        vb = last["vb"]
+        r, m = vb.records, int(vb.records.n)
+        arrs.update({k: getattr(r, k) for k in ("chrom", "pos", "allele_off", "ref_len", "alt_len", "ext_id",
+                                                       "heap") if getattr(r, k) is not None})
+        arrs.update(rec_line=vb.rec_line[:m], rec_alt=vb.rec_alt[:m])
+    elif name == "load":
+        fr = last["fr"]
+        arrs.update(copy=fr.copy, mapping=fr.mapping, copy_off=fr.copy_off, map_off=fr.map_off,
+                    line_state=fr.line_state, format_counters=fr.counters)
+    return arrs
+
+
 def parse():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--steps", type=int, default=20, help="timed steps (>= 1)")
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--full", action="store_true",
+                    help="also everything beside the headline figure: the CPU baselines, the keyed C4k step riding "
+                         "on the default line, the per-stage event pass and the roofline accounting (a plain run "
+                         "sets up, warms up, times the steps and prints the result line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step computed as DIR/<name>.npy "
+                         "(float32 / float64; a fixed seeded sample of the large arrays)")
     ap.add_argument("--workload", default="c2", choices=sorted(WORKLOADS))
     ap.add_argument("--n", type=int, default=None, help="records per GPU (default: config size)")
     ap.add_argument("--cpu-baseline", default="auto", choices=["auto", "on", "off"])
@@ -600,7 +665,11 @@ def dry_run(a):
 
 def main():
     a = parse()
+    if a.steps < 1:
+        raise SystemExit("bench.py: --steps must be at least 1")
     if a.workload == "dropin":
+        if a.dump_outputs:
+            raise SystemExit("bench.py: --dump-outputs: the dropin workload has no timed steps to dump")
         torch.cuda.set_device(0)
         dropin(a)
         return
@@ -611,18 +680,19 @@ def main():
         return
     from annotatedvdb_amd import distributed as D
     ri = D.rank_info()
-    # the north_star path rides along the default line: the keyed 1B-shard step (C4k)
-    keyed = a.keyed == "on" or (a.keyed == "auto" and a.workload == "c2")
-    # CPU baselines first, before this process touches the GPU (their worker
+    # --full: the north_star path rides along the default line: the keyed 1B-shard step (C4k)
+    keyed = a.full and (a.keyed == "on" or (a.keyed == "auto" and a.workload == "c2"))
+    # --full: CPU baselines first, before this process touches the GPU (their worker
     # processes are forked and must not inherit an initialised HIP runtime)
-    want_cpu = a.cpu_baseline == "on" or (a.cpu_baseline == "auto" and ri.world == 1
-                                          and a.workload in ("c1", "c2", "c3", "c4", "c5", "c4k", "load", "vcf"))
+    want_cpu = a.full and (a.cpu_baseline == "on" or (
+        a.cpu_baseline == "auto" and ri.world == 1
+        and a.workload in ("c1", "c2", "c3", "c4", "c5", "c4k", "load", "vcf")))
     cpu = cpu_baseline(a.workload, a.cpu_seconds) if (ri.rank == 0 and want_cpu) else None
     cpu_k = cpu_baseline("c4k", a.cpu_seconds) if (keyed and ri.rank == 0 and want_cpu) else None
     ri = D.init("nccl")
     dev = torch.device("cuda", D.device_index(ri))
     torch.cuda.set_device(dev)
-    out = run_workload(a, a.workload, ri, dev, cpu)
+    out = run_workload(a, a.workload, ri, dev, cpu, dump_dir=a.dump_outputs if ri.rank == 0 else None)
     if keyed:
         torch.cuda.empty_cache()
         k = run_workload(a, "c4k", ri, dev, cpu_k)
@@ -636,9 +706,11 @@ def main():
     D.finalize(ri)
 
 
-def run_workload(a, name, ri, dev, cpu):
+def run_workload(a, name, ri, dev, cpu, dump_dir=None):
     """One workload on this rank's GPU: resident synthetic batch, warmup, K timed
-    steps between barriers, max over ranks; returns the JSON object."""
+    steps between barriers, max over ranks; returns the JSON object.  ``dump_dir``:
+    --dump-outputs.  Without --full nothing runs after the timed steps: no stage
+    pass, no roofline accounting."""
     from annotatedvdb_amd import distributed as D
     from annotatedvdb_amd import synth
     from annotatedvdb_amd.engine import Engine
@@ -733,7 +805,9 @@ def run_workload(a, name, ri, dev, cpu):
         elif name == "vcf":
             # (records only: the public 80-byte line table is for the load path, K5)
             count_free = os.environ.get("AVDB_BENCH_VCF_COUNTED", "0") != "1"  # (A/B: the counted records path)
-            timed("vcf_tokenize", record, lambda: eng.vcf_tokenize(text, want_lines=False, count_free=count_free))
+            last.pop("vb", None)  # (the last step's batch, for --dump-outputs; freed before the next one)
+            timed("vcf_tokenize", record, lambda: last.setdefault(
+                "vb", eng.vcf_tokenize(text, want_lines=False, count_free=count_free)))
         elif name == "load":
             box = {}
             timed("vcf_tokenize", record, lambda: box.setdefault("vb", eng.vcf_tokenize(text)))
@@ -747,8 +821,8 @@ def run_workload(a, name, ri, dev, cpu):
             ps.run(evs if record else None)
 
     last = {}
-    # (AVDB_BENCH_STAGE_EVENTS=0: no stage-breakdown pass after the timed region)
-    stage_events = os.environ.get("AVDB_BENCH_STAGE_EVENTS", "1") != "0"
+    # (--full; AVDB_BENCH_STAGE_EVENTS=0: no stage-breakdown pass after the timed region)
+    stage_events = a.full and os.environ.get("AVDB_BENCH_STAGE_EVENTS", "1") != "0"
     for _ in range(a.warmup):
         step(False)
     use_graph = a.graph == "on" or (a.graph == "auto" and name == "c1")
@@ -790,6 +864,8 @@ def run_workload(a, name, ri, dev, cpu):
     torch.cuda.synchronize()
     elapsed = D.max_over_ranks(time.perf_counter() - t0, ri, device=dev)
     loop_ms = loop0.elapsed_time(loop1) / a.steps
+    if dump_dir:
+        dump_outputs(dump_dir, step_outputs(name, n, code, hist, ctr, ks or ps, last))
     # the stage breakdown: the same steps again after the timed region, plain launches
     # with an event pair per stage on the stream it ran on
     if stage_events:
@@ -800,15 +876,43 @@ def run_workload(a, name, ri, dev, cpu):
     stage_ms["timed_step_events"] = loop_ms
     if graph is not None:
         stage_ms["graph_replay"] = True
+    if name in ("vcf", "load"):
+        n_lines, n = n, n_rec  # the unit is emitted variant records (per-ALT rows)
+    total_records = n * ri.world * a.steps
+    value = total_records / elapsed
+    out = {
+        "metric": METRIC,
+        "value": value,
+        "unit": "variants/s",
+        "n_gpus": ri.world,
+        "steps": a.steps,
+        "warmup": a.warmup,
+        "ms_per_step": elapsed * 1e3 / a.steps,
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "u8" if name in ("c1", "c4k", "load", "vcf") else "u32",
+        "data": {"c4k": "synthetic dbSNP-mix records (synth.dbsnp_alleles, torch PCG on device), resident in HBM",
+                 "c1": "synthetic C1 records (numpy PCG64 seed 1, synth.np_c1), resident in HBM",
+                 "load": "synthetic dbSNP-shaped VCF text with INFO FREQ (numpy PCG64 lines tiled on the device)",
+                 "vcf": "synthetic dbSNP-shaped VCF text (numpy PCG64 lines tiled on the device)"}.get(
+                     name, "synthetic (seeded GRCh38-shaped records generated on device)"),
+        "config": {"workload": W["desc"], "records_per_gpu": n, "records_total": n * ri.world,
+                   "parallelism": f"dp{ri.world} (length-balanced 64 Mb genome pieces per rank)",
+                   "records_processed": int(node_ctr[20].item()) // max(1, a.steps),
+                   "exchange": ex.kind if ri.distributed or not isinstance(ex, D.TorchExchange) else None,
+                   "stage_ms": stage_ms},
+    }
+    if name in ("vcf", "load"):
+        out["config"]["records_processed"] = None
+    if not a.full:
+        ex.close()
+        return out
     # the roofline's kernel time: the one-kernel steps (C2/C3/C4) and the whole-step
     # workloads (C1, C4k, vcf) from the timed loop's own events; C5's K2 and the load
     # workload's K5 write pass from the stage breakdown
     kname = {"c5": "record_prep", "load": "format_write"}.get(name)
     kern_ms = stage_ms[kname] if kname else loop_ms
-    if name in ("vcf", "load"):
-        n_lines, n = n, n_rec  # the unit is emitted variant records (per-ALT rows)
-    total_records = n * ri.world * a.steps
-    value = total_records / elapsed
 
     if name == "c4k":
         # SURVEY.md §8d per-record bytes of the keyed record path (34 + rlen + alen + 24 per
@@ -890,30 +994,11 @@ def run_workload(a, name, ri, dev, cpu):
         except Exception:
             traffic = None
 
-    out = {
-        "metric": METRIC,
-        "value": value,
-        "unit": "variants/s",
-        "n_gpus": ri.world,
-        "steps": a.steps,
-        "warmup": a.warmup,
-        "ms_per_step": elapsed * 1e3 / a.steps,
-        "higher_is_better": True,
-        "scaling": "weak",
-        "vs_baseline": None,
-        "dtype": "u32",
-        "data": "synthetic (seeded GRCh38-shaped records generated on device)",
-        "config": {"workload": W["desc"], "records_per_gpu": n, "records_total": n * ri.world,
-                   "parallelism": f"dp{ri.world} (length-balanced 64 Mb genome pieces per rank)",
-                   "records_processed": int(node_ctr[20].item()) // max(1, a.steps),
-                   "exchange": ex.kind if ri.distributed or not isinstance(ex, D.TorchExchange) else None,
-                   "stage_ms": stage_ms},
-        "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                     "frac": achieved / HBM_PEAK_GBS, "traffic": traffic,
-                     "kernel": W["kernel"], "kernel_ms": kern_ms,
-                     "algorithmic_bytes_per_launch": bytes_per_launch},
-        "cpu_baseline": cpu,
-    }
+    out["roofline"] = {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                       "frac": achieved / HBM_PEAK_GBS, "traffic": traffic,
+                       "kernel": W["kernel"], "kernel_ms": kern_ms,
+                       "algorithmic_bytes_per_launch": bytes_per_launch}
+    out["cpu_baseline"] = cpu
     if name == "c5":
         out["roofline"]["line_granular"] = {
             "bytes_per_launch": line_bytes, "achieved": line_bytes / (kern_ms * 1e-3) / 1e9,
@@ -947,8 +1032,6 @@ def run_workload(a, name, ri, dev, cpu):
                                     "note": pk.get("note")}
     if name == "c4k":
         kt = ks.kt
-        out["dtype"] = "u8"
-        out["data"] = "synthetic dbSNP-mix records (synth.dbsnp_alleles, torch PCG on device), resident in HBM"
         out["config"].update(key_bytes=int(kt.key_offsets(n)[n].item()), path_bytes=int(kt.path_offsets(n)[n].item()),
                              long_records=n_long, heap_bytes=heap_bytes,
                              duplicates=int(node_ctr[21].item()) // max(1, a.steps))
@@ -986,8 +1069,6 @@ def run_workload(a, name, ri, dev, cpu):
                                    "pass with an event pair per stage")
     if name == "c1":
         kt = ks.kt
-        out["dtype"] = "u8"
-        out["data"] = "synthetic C1 records (numpy PCG64 seed 1, synth.np_c1), resident in HBM"
         out["config"].update(key_bytes=int(kt.key_offsets(n)[n].item()), path_bytes=int(kt.path_offsets(n)[n].item()),
                              duplicates=int(node_ctr[21].item()) // max(1, a.steps))
         out["roofline"]["note"] = ("achieved = SURVEY 8d record bytes + key/path text written / whole step "
@@ -998,18 +1079,12 @@ def run_workload(a, name, ri, dev, cpu):
             out["cpu_baseline"]["reference_survey_per_core"] = "285-306 K variants/s (SURVEY.md 6, build container)"
     if name == "load":
         fr = last["fr"]
-        out["dtype"] = "u8"
-        out["data"] = "synthetic dbSNP-shaped VCF text with INFO FREQ (numpy PCG64 lines tiled on the device)"
         out["config"].update(host_lines=int(fr.counters[27].item()), lines_per_gpu=n_lines, text_bytes_per_gpu=int(text.numel()),
-                             copy_bytes_per_gpu=int(fr.copy.numel()), mapping_bytes_per_gpu=int(fr.mapping.numel()),
-                             records_processed=None)
+                             copy_bytes_per_gpu=int(fr.copy.numel()), mapping_bytes_per_gpu=int(fr.mapping.numel()))
         out["roofline"]["note"] = ("achieved = K5 write-pass algorithmic bytes (text + line table + offsets "
                                    "+ per-record inputs + COPY/.mapping text written) / its HIP-event time")
     if name == "vcf":
-        out["dtype"] = "u8"
-        out["data"] = "synthetic dbSNP-shaped VCF text (numpy PCG64 lines tiled on the device)"
-        out["config"].update(lines_per_gpu=n_lines, text_bytes_per_gpu=int(text.numel()),
-                             records_processed=None)
+        out["config"].update(lines_per_gpu=n_lines, text_bytes_per_gpu=int(text.numel()))
         out["roofline"]["note"] = ("achieved = algorithmic bytes / whole tokenize step, records only "
                                    "(vcf_tokenize(want_lines=False), the count-free path: window parse into "
                                    "window-local line slots, two window-total scans, one host read, per-window "

@@ -8,7 +8,7 @@ mkdir -p "$OUT"
 for rep in 1 2; do
   for cfg in "fork:auto:10" "fork:auto:50" "serial:auto:50" "fork:off:50"; do
     IFS=: read lay gr st <<< "$cfg"
-    AVDB_BENCH_LAYOUT=$lay timeout -k 10 200 python bench.py --workload c1 --steps $st --warmup 3 --graph $gr \
+    AVDB_BENCH_LAYOUT=$lay timeout -k 10 200 python bench.py --full --workload c1 --steps $st --warmup 3 --graph $gr \
       --cpu-baseline off > "$OUT/c1_${lay}_${gr}_${st}_$rep.json" 2>&1 || { tail -5 "$OUT/c1_${lay}_${gr}_${st}_$rep.json"; exit 1; }
     python3 - "$OUT/c1_${lay}_${gr}_${st}_$rep.json" "$cfg" <<'PY'
 import json, sys

@@ -13,7 +13,7 @@ for c in $CASES; do
   IFS=: read -r L G K <<< "$c"
   K=${K:-0}
   tag="${L}_${G}_${K}"
-  timeout -k 10 300 env AVDB_BENCH_LAYOUT=$L AVDB_BENCH_K4_GRID=$G AVDB_BENCH_K7_GRID=$K python bench.py \
+  timeout -k 10 300 env AVDB_BENCH_LAYOUT=$L AVDB_BENCH_K4_GRID=$G AVDB_BENCH_K7_GRID=$K python bench.py --full \
       --workload c4k --steps 10 --warmup 3 --cpu-baseline off > "$OUT/c4k_$tag.json" 2> "$OUT/c4k_$tag.err"
   rc=$?
   [ $rc -ne 0 ] && { echo "FAIL $c rc=$rc"; tail -5 "$OUT/c4k_$tag.err"; exit $rc; }

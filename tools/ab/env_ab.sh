@@ -10,10 +10,10 @@ export TMPDIR=/tmp
 for rep in 1 2; do
   for kv in base "$@"; do
     if [ "$kv" = base ]; then
-      timeout -k 10 300 python bench.py --workload "$W" --steps 10 --warmup 3 --cpu-baseline off \
+      timeout -k 10 300 python bench.py --full --workload "$W" --steps 10 --warmup 3 --cpu-baseline off \
         > "$OUT/${W}_${kv}_$rep.log" 2>&1 || { tail -20 "$OUT/${W}_${kv}_$rep.log"; exit 1; }
     else
-      env "$kv" timeout -k 10 300 python bench.py --workload "$W" --steps 10 --warmup 3 --cpu-baseline off \
+      env "$kv" timeout -k 10 300 python bench.py --full --workload "$W" --steps 10 --warmup 3 --cpu-baseline off \
         > "$OUT/${W}_${kv}_$rep.log" 2>&1 || { tail -20 "$OUT/${W}_${kv}_$rep.log"; exit 1; }
     fi
     python3 - "$OUT/${W}_${kv}_$rep.log" "$kv" <<'PY'

@@ -23,7 +23,7 @@ for rep in 1 2; do
 done
 for lib in $LIBS; do
   v=$(basename "$lib" .so)
-  AVDB_LIB=$lib timeout -k 10 300 python bench.py --workload c4k --steps 10 --warmup 3 --cpu-baseline off \
+  AVDB_LIB=$lib timeout -k 10 300 python bench.py --full --workload c4k --steps 10 --warmup 3 --cpu-baseline off \
     > "$OUT/bench_c4k_$v.log" 2>&1 || exit 1
   python - "$OUT/bench_c4k_$v.log" <<'PY'
 import json, sys

@@ -18,7 +18,7 @@ done
 for rep in 1 2; do
   for lib in $LIBS; do
     v=$(basename "$lib" .so)
-    AVDB_LIB=$lib timeout -k 10 300 python bench.py --workload c4k --steps 10 --warmup 3 --cpu-baseline off \
+    AVDB_LIB=$lib timeout -k 10 300 python bench.py --full --workload c4k --steps 10 --warmup 3 --cpu-baseline off \
       > "$OUT/c4k_${v}_$rep.json" 2> "$OUT/c4k_${v}_$rep.err" || { tail -5 "$OUT/c4k_${v}_$rep.err"; exit 1; }
     python - "$OUT/c4k_${v}_$rep.json" "$v" <<'PY'
 import json, sys

@@ -9,8 +9,9 @@ AVDB_LIB=annotatedvdb_amd/_lib/var/libavdb_k5split.so timeout -k 10 600 python -
 tail -2 gpurun_out/r05c/pytest_k5split.log
 bash tools/ab/c4k_layout_ab.sh r05c_ab serial:0:0 overlap:256:2048 overlap:512:1024 overlap:256:3072 serial:0:2048 serial:0:3072 serial:0:0 || exit 1
 for lib in annotatedvdb_amd/_lib/libavdb_hip.so annotatedvdb_amd/_lib/var/libavdb_k5split.so annotatedvdb_amd/_lib/libavdb_hip.so annotatedvdb_amd/_lib/var/libavdb_k5split.so; do
-  AVDB_LIB=$lib timeout -k 10 300 python bench.py --workload load --steps 10 --warmup 3 --cpu-baseline off > gpurun_out/r05c/load_$(basename $lib .so).json 2>gpurun_out/r05c/load.err || { tail -5 gpurun_out/r05c/load.err; exit 1; }
+  O=$(ls -d */r05c)  # (the log directory made above)
+  AVDB_LIB=$lib timeout -k 10 300 python bench.py --full --workload load --steps 10 --warmup 3 --cpu-baseline off > "$O/load_$(basename $lib .so).json" 2>"$O/load.err" || { tail -5 "$O/load.err"; exit 1; }
   python -c "
-import json,sys; d=json.loads(open('gpurun_out/r05c/load_$(basename $lib .so).json').read().strip().splitlines()[-1]); print('$lib', d['ms_per_step'], d['config']['stage_ms'])"
+import json,sys; d=json.loads(open('$O/load_$(basename $lib .so).json').read().strip().splitlines()[-1]); print('$lib', d['ms_per_step'], d['config']['stage_ms'])"
 done
 echo DONE

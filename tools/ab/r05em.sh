@@ -14,7 +14,7 @@ tail -1 "$OUT/pytest.log"
 for rep in 1 2; do
   for lib in $LIBS; do
     v=$(basename "$lib" .so)
-    AVDB_LIB=$lib timeout -k 10 300 python bench.py --workload vcf --steps 20 --warmup 3 --cpu-baseline off \
+    AVDB_LIB=$lib timeout -k 10 300 python bench.py --full --workload vcf --steps 20 --warmup 3 --cpu-baseline off \
       > "$OUT/vcf_${v}_$rep.json" 2> "$OUT/vcf_${v}_$rep.err" || { tail -5 "$OUT/vcf_${v}_$rep.err"; exit 1; }
     python - "$OUT/vcf_${v}_$rep.json" "$v" <<'PY'
 import json, sys
@@ -26,7 +26,7 @@ done
 for lib in $LIBS; do
   v=$(basename "$lib" .so)
   AVDB_LIB=$lib timeout -k 10 300 rocprofv3 --kernel-trace --stats -d "$OUT/prof_$v" -o run --output-format csv \
-    -- python bench.py --workload vcf --steps 20 --warmup 3 --cpu-baseline off > "$OUT/rocprof_$v.log" 2>&1 \
+    -- python bench.py --full --workload vcf --steps 20 --warmup 3 --cpu-baseline off > "$OUT/rocprof_$v.log" 2>&1 \
     || { tail -5 "$OUT/rocprof_$v.log"; exit 1; }
   python - "$OUT/prof_$v" "$v" <<'PY'
 import csv, glob, sys

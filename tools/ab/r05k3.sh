@@ -14,7 +14,7 @@ for rep in 1 2; do
   for lib in ${LIBS:-annotatedvdb_amd/_lib/libavdb_hip.so annotatedvdb_amd/_lib/var/libavdb_r05base.so}; do
     v=$(basename "$lib" .so)
     for w in c4k c1; do
-      AVDB_LIB=$lib timeout -k 10 300 python bench.py --workload $w --steps 10 --warmup 3 --cpu-baseline off \
+      AVDB_LIB=$lib timeout -k 10 300 python bench.py --full --workload $w --steps 10 --warmup 3 --cpu-baseline off \
         > "$OUT/${w}_${v}_$rep.json" 2> "$OUT/${w}_${v}_$rep.err" || { tail -5 "$OUT/${w}_${v}_$rep.err"; exit 1; }
       python - "$OUT/${w}_${v}_$rep.json" "$w $v" <<'PY'
 import json, sys

@@ -13,7 +13,7 @@ export TMPDIR=/tmp
 [ -n "$PROF_ONLY" ] || tail -1 "$OUT/pytest.log"
 for rep in $([ -n "$PROF_ONLY" ] || echo 1 2); do
   for counted in 0 1; do
-    AVDB_BENCH_VCF_COUNTED=$counted timeout -k 10 300 python bench.py --workload vcf --steps 20 --warmup 3 \
+    AVDB_BENCH_VCF_COUNTED=$counted timeout -k 10 300 python bench.py --full --workload vcf --steps 20 --warmup 3 \
       --cpu-baseline off > "$OUT/vcf_c${counted}_$rep.json" 2> "$OUT/vcf_c${counted}_$rep.err" \
       || { tail -5 "$OUT/vcf_c${counted}_$rep.err"; exit 1; }
     python - "$OUT/vcf_c${counted}_$rep.json" "counted=$counted" <<'PY'
@@ -25,7 +25,7 @@ PY
 done
 for counted in 0 1; do
   AVDB_BENCH_VCF_COUNTED=$counted timeout -k 10 300 rocprofv3 --kernel-trace --stats -d "$OUT/prof_c$counted" \
-    -o run --output-format csv -- python bench.py --workload vcf --steps 20 --warmup 3 --cpu-baseline off > "$OUT/rocprof_c$counted.log" 2>&1 \
+    -o run --output-format csv -- python bench.py --full --workload vcf --steps 20 --warmup 3 --cpu-baseline off > "$OUT/rocprof_c$counted.log" 2>&1 \
     || { tail -5 "$OUT/rocprof_c$counted.log"; exit 1; }
   python - "$OUT/prof_c$counted" "counted=$counted" <<'PY'
 import csv, glob, sys

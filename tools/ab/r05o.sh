@@ -10,7 +10,7 @@ bash tools/ab/r05j.sh "$T" || exit 1
 for rep in 1 2; do
   for lib in annotatedvdb_amd/_lib/libavdb_hip.so $(ls annotatedvdb_amd/_lib/var/libavdb_*.so 2>/dev/null); do
     v=$(basename "$lib" .so)
-    AVDB_LIB=$lib timeout -k 10 300 python bench.py --workload load --steps 10 --warmup 3 --cpu-baseline off \
+    AVDB_LIB=$lib timeout -k 10 300 python bench.py --full --workload load --steps 10 --warmup 3 --cpu-baseline off \
       > "$OUT/load_${v}_$rep.log" 2>&1 || { tail -5 "$OUT/load_${v}_$rep.log"; exit 1; }
     python3 - "$OUT/load_${v}_$rep.log" "$v" <<'PY'
 import json, sys

@@ -11,7 +11,7 @@ for rep in 1 2; do
   for lib in annotatedvdb_amd/_lib/libavdb_hip.so annotatedvdb_amd/_lib/var/libavdb_pw5.so; do
     v=$(basename "$lib" .so)
     for w in vcf load; do
-      AVDB_BENCH_VCF_COUNTED=1 AVDB_LIB=$lib timeout -k 10 300 python bench.py --workload $w --steps 20 --warmup 3 \
+      AVDB_BENCH_VCF_COUNTED=1 AVDB_LIB=$lib timeout -k 10 300 python bench.py --full --workload $w --steps 20 --warmup 3 \
         --cpu-baseline off > "$OUT/${w}_${v}_$rep.json" 2> "$OUT/${w}_${v}_$rep.err" || { tail -5 "$OUT/${w}_${v}_$rep.err"; exit 1; }
       python - "$OUT/${w}_${v}_$rep.json" "$w $v" <<'PY'
 import json, sys

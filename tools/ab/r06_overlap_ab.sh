@@ -5,7 +5,7 @@
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/../..}"
 OUT=gpurun_out/${1:-r06h}; mkdir -p "$OUT"; export TMPDIR=/tmp
 run() {  # name lib layout k4grid k7grid
-  timeout -k 10 300 env AVDB_LIB=$2 AVDB_BENCH_LAYOUT=$3 AVDB_BENCH_K4_GRID=$4 AVDB_BENCH_K7_GRID=$5 python bench.py --steps 8 --warmup 2 --cpu-baseline off --workload c4k > "$OUT/bench_$1.log" 2>&1 || exit $?
+  timeout -k 10 300 env AVDB_LIB=$2 AVDB_BENCH_LAYOUT=$3 AVDB_BENCH_K4_GRID=$4 AVDB_BENCH_K7_GRID=$5 python bench.py --full --steps 8 --warmup 2 --cpu-baseline off --workload c4k > "$OUT/bench_$1.log" 2>&1 || exit $?
   python - "$OUT/bench_$1.log" "$1" <<'PY'
 import json,sys
 d=json.loads([l for l in open(sys.argv[1]) if l.startswith('{')][-1])

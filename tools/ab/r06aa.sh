@@ -7,7 +7,7 @@ timeout -k 10 600 env AVDB_LIB=annotatedvdb_amd/_lib/var/libavdb_s64.so python -
 rc=$?; tail -1 "$OUT/pytest.log"; [ $rc -ne 0 ] && exit $rc
 for rep in 1 2; do
 for v in base s128 s64; do
-  timeout -k 10 300 env AVDB_LIB=annotatedvdb_amd/_lib/var/libavdb_$v.so python bench.py --steps 20 --warmup 5 --cpu-baseline off --workload vcf > "$OUT/bench_vcf_$v.log" 2>&1 || exit $?
+  timeout -k 10 300 env AVDB_LIB=annotatedvdb_amd/_lib/var/libavdb_$v.so python bench.py --full --steps 20 --warmup 5 --cpu-baseline off --workload vcf > "$OUT/bench_vcf_$v.log" 2>&1 || exit $?
   python - "$OUT/bench_vcf_$v.log" "vcf $v" <<'PY'
 import json,sys
 d=json.loads([l for l in open(sys.argv[1]) if l.startswith('{')][-1])

@@ -8,7 +8,7 @@ rc=$?; tail -3 "$OUT/pytest.log"; [ $rc -ne 0 ] && exit $rc
 for rep in 1 2; do
 for arm in serial:0 early:0 early:512 early:256; do
   lay=${arm%%:*}; g=${arm##*:}
-  timeout -k 10 300 env AVDB_BENCH_LAYOUT=$lay AVDB_BENCH_K4_GRID=$g python bench.py --steps 10 --warmup 3 --cpu-baseline off --workload c4k > "$OUT/bench_${lay}_$g.log" 2>&1 || exit $?
+  timeout -k 10 300 env AVDB_BENCH_LAYOUT=$lay AVDB_BENCH_K4_GRID=$g python bench.py --full --steps 10 --warmup 3 --cpu-baseline off --workload c4k > "$OUT/bench_${lay}_$g.log" 2>&1 || exit $?
   python - "$OUT/bench_${lay}_$g.log" "$arm" <<'PY'
 import json,sys
 d=json.loads([l for l in open(sys.argv[1]) if l.startswith('{')][-1])

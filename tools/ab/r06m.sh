@@ -9,7 +9,7 @@ for rep in 1 2; do
 for lib in base new; do
   if [ $lib = base ]; then L=annotatedvdb_amd/_lib/var/libavdb_base.so; else L=annotatedvdb_amd/_lib/libavdb_hip.so; fi
   for wl in load vcf; do
-    timeout -k 10 300 env AVDB_LIB=$L python bench.py --steps 10 --warmup 3 --cpu-baseline off --workload $wl > "$OUT/bench_${wl}_$lib.log" 2>&1 || exit $?
+    timeout -k 10 300 env AVDB_LIB=$L python bench.py --full --steps 10 --warmup 3 --cpu-baseline off --workload $wl > "$OUT/bench_${wl}_$lib.log" 2>&1 || exit $?
     python - "$OUT/bench_${wl}_$lib.log" "$wl $lib" <<'PY'
 import json,sys
 d=json.loads([l for l in open(sys.argv[1]) if l.startswith('{')][-1])

@@ -8,7 +8,7 @@ timeout -k 10 900 python -u -m pytest "tests/test_gpu_parity.py::test_c5_all_sha
 rc=$?; tail -3 "$OUT/pytest.log"; [ $rc -ne 0 ] && exit $rc
 for rep in 1 2; do
 for v in 1 0; do
-  timeout -k 10 300 env AVDB_BENCH_C5_PLAIN=$v python bench.py --steps 20 --warmup 3 --cpu-baseline off --workload c5 > "$OUT/bench_c5_plain$v.log" 2>&1 || exit $?
+  timeout -k 10 300 env AVDB_BENCH_C5_PLAIN=$v python bench.py --full --steps 20 --warmup 3 --cpu-baseline off --workload c5 > "$OUT/bench_c5_plain$v.log" 2>&1 || exit $?
   python - "$OUT/bench_c5_plain$v.log" "c5 plain=$v" <<'PY'
 import json,sys
 d=json.loads([l for l in open(sys.argv[1]) if l.startswith('{')][-1])

@@ -7,7 +7,7 @@ timeout -k 10 600 env AVDB_LIB=annotatedvdb_amd/_lib/var/libavdb_edge.so python 
 rc=$?; tail -2 "$OUT/pytest.log"; [ $rc -ne 0 ] && exit $rc
 for rep in 1 2 3; do
 for v in base edge; do
-  timeout -k 10 300 env AVDB_LIB=annotatedvdb_amd/_lib/var/libavdb_$v.so python bench.py --steps 10 --warmup 3 --cpu-baseline off --workload c4k > "$OUT/bench_c4k_$v.log" 2>&1 || exit $?
+  timeout -k 10 300 env AVDB_LIB=annotatedvdb_amd/_lib/var/libavdb_$v.so python bench.py --full --steps 10 --warmup 3 --cpu-baseline off --workload c4k > "$OUT/bench_c4k_$v.log" 2>&1 || exit $?
   python - "$OUT/bench_c4k_$v.log" "c4k $v" <<'PY'
 import json,sys
 d=json.loads([l for l in open(sys.argv[1]) if l.startswith('{')][-1])

@@ -6,7 +6,7 @@ cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/../..}"
 OUT=gpurun_out/r06u; mkdir -p "$OUT"; export TMPDIR=/tmp
 for rep in 1 2; do
 for v in base l2sink; do
-  timeout -k 10 300 env AVDB_LIB=annotatedvdb_amd/_lib/var/libavdb_$v.so python bench.py --steps 10 --warmup 3 --cpu-baseline off --workload load > "$OUT/bench_load_$v.log" 2>&1 || exit $?
+  timeout -k 10 300 env AVDB_LIB=annotatedvdb_amd/_lib/var/libavdb_$v.so python bench.py --full --steps 10 --warmup 3 --cpu-baseline off --workload load > "$OUT/bench_load_$v.log" 2>&1 || exit $?
   python - "$OUT/bench_load_$v.log" "load $v" <<'PY'
 import json,sys
 d=json.loads([l for l in open(sys.argv[1]) if l.startswith('{')][-1])

@@ -15,7 +15,7 @@ LIBS="annotatedvdb_amd/_lib/libavdb_hip.so $(ls annotatedvdb_amd/_lib/var/libavd
 for rep in 1 2; do
   for lib in $LIBS; do
     v=$(basename "$lib" .so)
-    AVDB_LIB=$lib timeout -k 10 300 python bench.py --workload "$W" --steps 10 --warmup 3 --cpu-baseline off \
+    AVDB_LIB=$lib timeout -k 10 300 python bench.py --full --workload "$W" --steps 10 --warmup 3 --cpu-baseline off \
       > "$OUT/${W}_${v}_$rep.log" 2>&1 || exit 1
     python3 - "$OUT/${W}_${v}_$rep.log" "$v" <<'PY'
 import json, sys

@@ -22,14 +22,14 @@ if [ "$MODE" = all ] || [ "$MODE" = test ]; then
   step smoke 300 python __graft_entry__.py smoke
 fi
 if [ "$MODE" = all ] || [ "$MODE" = bench ]; then
-  step bench_c2 600 python bench.py --steps 20 --warmup 3
-  step bench_c3 600 python bench.py --steps 20 --warmup 3 --workload c3 --cpu-baseline off
-  step bench_c5 600 python bench.py --steps 5 --warmup 2 --workload c5
+  step bench_c2 600 python bench.py --full --steps 20 --warmup 3
+  step bench_c3 600 python bench.py --full --steps 20 --warmup 3 --workload c3 --cpu-baseline off
+  step bench_c5 600 python bench.py --full --steps 5 --warmup 2 --workload c5
 fi
 if [ "$MODE" = all ] || [ "$MODE" = prof ]; then
   export TMPDIR=/tmp
-  step rocprof_c2 600 rocprofv3 --kernel-trace --stats -d "$OUT/prof_c2" -o run --output-format csv -- python3 "$R/bench.py" --steps 10 --warmup 2 --cpu-baseline off
-  step pmc_fetch_c2 600 rocprofv3 --pmc FETCH_SIZE -d "$OUT/pmc_fetch_c2" -o run --output-format csv -- python3 "$R/bench.py" --steps 5 --warmup 1 --cpu-baseline off
-  step pmc_write_c2 600 rocprofv3 --pmc WRITE_SIZE -d "$OUT/pmc_write_c2" -o run --output-format csv -- python3 "$R/bench.py" --steps 5 --warmup 1 --cpu-baseline off
+  step rocprof_c2 600 rocprofv3 --kernel-trace --stats -d "$OUT/prof_c2" -o run --output-format csv -- python3 "$R/bench.py" --full --steps 10 --warmup 2 --cpu-baseline off
+  step pmc_fetch_c2 600 rocprofv3 --pmc FETCH_SIZE -d "$OUT/pmc_fetch_c2" -o run --output-format csv -- python3 "$R/bench.py" --full --steps 5 --warmup 1 --cpu-baseline off
+  step pmc_write_c2 600 rocprofv3 --pmc WRITE_SIZE -d "$OUT/pmc_write_c2" -o run --output-format csv -- python3 "$R/bench.py" --full --steps 5 --warmup 1 --cpu-baseline off
 fi
 echo DONE

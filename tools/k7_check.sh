@@ -9,7 +9,7 @@ timeout -k 10 600 python -u -m pytest tests/test_gpu_c1.py tests/test_gpu_c4k.py
   --timeout-method thread -p no:cacheprovider > "$OUT/pytest.log" 2>&1 || { tail -30 "$OUT/pytest.log"; exit 1; }
 tail -2 "$OUT/pytest.log"
 for k in 1 2; do
-  timeout -k 10 300 python bench.py --workload c4k --steps 10 --warmup 3 --cpu-baseline off > "$OUT/bench_c4k_$k.log" 2>&1 || exit 1
+  timeout -k 10 300 python bench.py --full --workload c4k --steps 10 --warmup 3 --cpu-baseline off > "$OUT/bench_c4k_$k.log" 2>&1 || exit 1
   python - "$OUT/bench_c4k_$k.log" <<'PY'
 import json, sys
 d = json.loads([x for x in open(sys.argv[1]) if x.startswith("{")][-1])

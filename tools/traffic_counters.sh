@@ -8,6 +8,6 @@ cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 W=$1; O=gpurun_out/${2:-traffic_$W}
 mkdir -p "$O"
 export TMPDIR=/tmp
-timeout -s KILL 200 rocprofv3 --pmc TCC_EA0_RDREQ_32B_sum TCC_EA0_RDREQ_64B_sum TCC_EA0_RDREQ_128B_sum TCC_EA0_RDREQ_DRAM_32B_sum -d "$O/rd" -o run --output-format csv -- python3 bench.py --workload "$W" --steps 2 --warmup 1 --cpu-baseline off > "$O/rd.log" 2>&1 &&
-timeout -s KILL 200 rocprofv3 --pmc TCC_EA0_WRREQ_sum TCC_EA0_WRREQ_64B_sum TCC_EA0_WRREQ_WRITE_DRAM_32B_sum -d "$O/wr" -o run --output-format csv -- python3 bench.py --workload "$W" --steps 2 --warmup 1 --cpu-baseline off > "$O/wr.log" 2>&1 &&
+timeout -s KILL 200 rocprofv3 --pmc TCC_EA0_RDREQ_32B_sum TCC_EA0_RDREQ_64B_sum TCC_EA0_RDREQ_128B_sum TCC_EA0_RDREQ_DRAM_32B_sum -d "$O/rd" -o run --output-format csv -- python3 bench.py --full --workload "$W" --steps 2 --warmup 1 --cpu-baseline off > "$O/rd.log" 2>&1 &&
+timeout -s KILL 200 rocprofv3 --pmc TCC_EA0_WRREQ_sum TCC_EA0_WRREQ_64B_sum TCC_EA0_WRREQ_WRITE_DRAM_32B_sum -d "$O/wr" -o run --output-format csv -- python3 bench.py --full --workload "$W" --steps 2 --warmup 1 --cpu-baseline off > "$O/wr.log" 2>&1 &&
 python3 tools/prof_summary.py traffic "$O/rd" "$O/wr" > "$O/traffic.json" && cat "$O/traffic.json"
