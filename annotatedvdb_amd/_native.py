@@ -57,6 +57,11 @@ MATCH_NONE, MATCH_EXACT, MATCH_SWITCHED, MATCH_HOST = 0, 1, 2, 255
 LINE_GPU, LINE_HOST, LINE_SKIP = 0, 1, 2
 KEY_OK, KEY_HOST, KEY_NEED_DIGEST, KEY_OVERFLOW, KEY_DIGEST_PENDING = 0, 1, 2, 3, 4
 PATH_OVERFLOW = 0x10
+CADD_N_CONTIGS = 25
+CADD_ROW_SCORE_HOST, CADD_ROW_BAD = 1, 2
+CADD_NONE, CADD_SNV, CADD_INDEL, CADD_HOST = 0, 1, 2, 255
+CADD_COUNT_ROWS, CADD_COUNT_SCORE_HOST, CADD_COUNT_BAD, CADD_COUNT_ORDER_VIOLATIONS, CADD_N_COUNTS = 0, 1, 2, 3, 4
+CADD_CTR_SNV, CADD_CTR_INDEL, CADD_CTR_NOT_MATCHED, CADD_N_CTRS = 0, 1, 2, 3
 MAX_ALG_ID = 64
 
 
@@ -75,6 +80,17 @@ class VcfOpts(ctypes.Structure):
 
     def __init__(self, min_fields: int = 0, chrom_map=None):
         super().__init__(ctypes.sizeof(VcfOpts), min_fields, chrom_map)
+
+
+class CaddTableView(ctypes.Structure):
+    """avdb_cadd_table (include/avdb.h); ``struct_size`` is filled in."""
+    _fields_ = [("struct_size", ctypes.c_uint32), ("reserved", ctypes.c_uint32), ("n_rows", ctypes.c_uint64),
+                ("text", ctypes.c_void_p), ("text_bytes", ctypes.c_uint64)] + \
+               [(name, ctypes.c_void_p) for name in ("chrom", "pos", "ref_off", "ref_len", "alt_off", "alt_len", "raw",
+                                                     "phred", "flags", "first_row", "end_row")]
+
+    def __init__(self, n_rows: int = 0, text=None, text_bytes: int = 0, *columns):
+        super().__init__(ctypes.sizeof(CaddTableView), 0, n_rows, text, text_bytes, *columns)
 
 
 class LineResult(ctypes.Structure):
@@ -108,6 +124,8 @@ EXPORTED_SYMBOLS = [
     "avdb_small_prep", "avdb_small_prep_host", "avdb_bin_path_host", "avdb_annotate_host", "avdb_host_alloc", "avdb_host_free",
     "avdb_rccl_unique_id", "avdb_rccl_comm_init", "avdb_rccl_comm_destroy",
     "avdb_hist_allgather_workspace_size", "avdb_hist_allgather",
+    "avdb_cadd_workspace_size", "avdb_cadd_table_build", "avdb_cadd_match",
+    "avdb_cadd_table_build_host", "avdb_cadd_match_host",
 ]
 
 
@@ -229,6 +247,12 @@ def _sig(lib):
     f.avdb_hist_allgather.argtypes = [P, P, P, SZ, P, SZ, P, P, P, SZ, P]
     f.avdb_vcf_select_lines.argtypes = [P, SZ, P, P, P, P, U32, U32, I32, P, SZ, P, P]
     f.avdb_vcf_select_copy.argtypes = [P, P, SZ, SZ, P, P, P, P]
+    f.avdb_cadd_workspace_size.argtypes = [SZ, SZ, ctypes.POINTER(SZ)]
+    f.avdb_cadd_table_build_host.argtypes = [P, P, SZ, SZ] + [P] * 12
+    f.avdb_cadd_table_build.argtypes = f.avdb_cadd_table_build_host.argtypes + [P, SZ, P]
+    f.avdb_cadd_match_host.argtypes = [P, ctypes.POINTER(CaddTableView), ctypes.POINTER(CaddTableView), P, P, P, P, P,
+                                       P, SZ, SZ, P, P, P, P, P]
+    f.avdb_cadd_match.argtypes = f.avdb_cadd_match_host.argtypes + [P]
     for name in EXPORTED_SYMBOLS:
         if name not in ("avdb_last_error",):
             getattr(f, name).restype = I32

@@ -1220,6 +1220,21 @@ extern "C" int avdb_vcf_count_lines(avdb_ctx* ctx, const uint8_t* text, size_t t
                     workspace_bytes >= count_ws_full(text_bytes));
 }
 
+// The count pass and the line-starts pass for another translation unit's text
+// (K10a's CADD slab): starts[0 .. n_lines) in order.  count_ws: at least
+// AVDB_VCF_COUNT_WORKSPACE_BYTES.
+int avdb::text_line_starts(const uint8_t* text, size_t text_bytes, size_t n_lines, void* count_ws, uint64_t* starts,
+                           hipStream_t s) {
+  if (n_lines == 0 || text_bytes == 0) return AVDB_OK;
+  if (int e = count_pass(text, text_bytes, count_ws, nullptr, s, false)) return e;
+  const char* cw = static_cast<const char*>(count_ws);
+  hipLaunchKernelGGL(k_vcf_starts, dim3(kVcfGrid), dim3(kBlock), 0, s, text, text_bytes,
+                     reinterpret_cast<const unsigned long long*>(cw + kCountWsBlkOff),
+                     reinterpret_cast<const uint32_t*>(cw + kCountWsWave), n_lines, starts);
+  AVDB_LAUNCH_CHECK("k_vcf_starts");
+  return AVDB_OK;
+}
+
 static int parse_lines(avdb_ctx* ctx, const uint8_t* text, size_t text_bytes, size_t n_lines,
                        const void* line_counts, size_t line_counts_bytes, void* workspace, size_t workspace_bytes,
                        avdb_vcf_line* lines, uint64_t* rec_off, uint64_t* heap_off, const avdb_vcf_opts* opts,

@@ -67,6 +67,34 @@ class RecordBatch:
         return self.heap is not None
 
 
+@dataclass
+class CaddColumns:
+    """A built CADD table (K10a, ``avdb_cadd_table``): the text slab the allele
+    offsets point into, one entry per data line in each column, the contig index
+    and the build's counts (``N.CADD_COUNT_*``, host)."""
+    text: torch.Tensor
+    n_rows: int
+    chrom: torch.Tensor
+    pos: torch.Tensor
+    ref_off: torch.Tensor
+    ref_len: torch.Tensor
+    alt_off: torch.Tensor
+    alt_len: torch.Tensor
+    raw: torch.Tensor
+    phred: torch.Tensor
+    flags: torch.Tensor
+    first_row: torch.Tensor
+    end_row: torch.Tensor
+    counts: np.ndarray
+
+    def view(self) -> "N.CaddTableView":
+        """The C struct over these tensors (valid while they are alive)."""
+        return N.CaddTableView(self.n_rows, N.ptr(self.text), self.text.numel(),
+                               *[N.ptr(getattr(self, f)) for f in ("chrom", "pos", "ref_off", "ref_len", "alt_off",
+                                                                    "alt_len", "raw", "phred", "flags", "first_row",
+                                                                    "end_row")])
+
+
 _RS_RE = re.compile(r"^rs([1-9][0-9]{0,17})$")
 
 
@@ -1299,6 +1327,92 @@ class Engine:
             key_off.numel() - 1, N.ptr(q) if q.numel() else None, N.ptr(q_off), N.ptr(skip), n, N.ptr(match),
             N.ptr(counters), self._stream()))
         return match[:n]
+
+    # -- K10: CADD table and allele join ---------------------------------------
+    def new_cadd_counters(self) -> torch.Tensor:
+        """``{snv, indel, not_matched}`` (``N.CADD_CTR_*``), added to by :meth:`cadd_match`."""
+        return torch.zeros(N.CADD_N_CTRS, dtype=torch.int64, device=self.device)
+
+    def _count_lines(self, text: torch.Tensor) -> int:
+        """Lines of a '\\n'-separated slab: newlines + (the text does not end in one)."""
+        nb = text.numel()
+        if nb == 0:
+            return 0
+        if self.host_only:
+            return int((text == 10).sum()) + int(text[-1] != 10)
+        ws = self.scratch("cadd_count", N.VCF_COUNT_WORKSPACE_BYTES)
+        cnt = self.empty(1, torch.int64)
+        N.check("avdb_vcf_count_lines", self.lib.avdb_vcf_count_lines(
+            self.ctx, N.ptr(text), nb, N.ptr(ws), ws.numel(), N.ptr(cnt), self._stream()))
+        return int(cnt.item()) + int(text[-1].item() != 10)
+
+    def cadd_table_build(self, text) -> "CaddColumns":
+        """K10a: a slab of uncompressed CADD TSV (bytes, numpy ``uint8`` or a ``uint8``
+        tensor) -> the table's columns on this engine's device.  One sync (the line
+        count) before the build, one after (the counts).  On a host-only engine the
+        library's host entry runs the same per-line code."""
+        if isinstance(text, (bytes, bytearray, memoryview)):
+            text = torch.from_numpy(np.frombuffer(bytes(text), dtype=np.uint8).copy()) if len(text) else \
+                torch.zeros(0, dtype=torch.uint8)
+        elif isinstance(text, np.ndarray):
+            text = torch.from_numpy(np.ascontiguousarray(text, dtype=np.uint8))
+        text = self._dev(text)
+        nb = text.numel()
+        n_lines = self._count_lines(text)
+        m = max(1, n_lines)
+        cols = [self.empty(m, dt) for dt in (torch.uint8, torch.int32, torch.int64, torch.int32, torch.int64,
+                                             torch.int32, torch.float64, torch.float64, torch.uint8)]
+        first_row = self.empty(N.CADD_N_CONTIGS, torch.int32)
+        end_row = self.empty(N.CADD_N_CONTIGS, torch.int32)
+        counts = self.empty(N.CADD_N_COUNTS, torch.int64)
+        args = [self.ctx, N.ptr(text) if nb else None, nb, n_lines] + [N.ptr(c) for c in cols] + \
+               [N.ptr(first_row), N.ptr(end_row), N.ptr(counts)]
+        if self.host_only:
+            N.check("avdb_cadd_table_build_host", self.lib.avdb_cadd_table_build_host(*args))
+        else:
+            sz = ctypes.c_size_t()
+            self.lib.avdb_cadd_workspace_size(nb, n_lines, ctypes.byref(sz))
+            ws = self.scratch("cadd_build", int(sz.value))
+            N.check("avdb_cadd_table_build", self.lib.avdb_cadd_table_build(
+                *args, N.ptr(ws), ws.numel(), self._stream()))
+        cnt = counts.cpu().numpy().astype(np.uint64)
+        n_rows = int(cnt[N.CADD_COUNT_ROWS])
+        return CaddColumns(text, n_rows, *[c[:n_rows] for c in cols], first_row, end_row, cnt)
+
+    def cadd_match(self, snv: Optional["CaddColumns"], indel: Optional["CaddColumns"], b: RecordBatch,
+                   counters: Optional[torch.Tensor] = None, out=None):
+        """K10b: ``(row int32[n], kind uint8[n], raw float64[n], phred float64[n])`` of
+        each record against the SNV or the indel table (either may be ``None``).
+        ``raw`` / ``phred`` are written for matched records only (NaN elsewhere in
+        buffers this call allocates; ``out``: the caller's four buffers, of which
+        only the first ``n`` entries are touched).  ``counters``: see
+        :meth:`new_cadd_counters`."""
+        b = b if b.device == self.device else b.to(self.device)
+        self._check_alleles(b)
+        n = b.n
+        for t in (snv, indel):
+            if t is not None and t.text.device != self.device:
+                raise ValueError("CADD table lives on another device than this engine")
+        if out is None:
+            row, kind = self.empty(max(1, n), torch.int32), self.empty(max(1, n), torch.uint8)
+            raw, phred = self.empty(max(1, n), torch.float64), self.empty(max(1, n), torch.float64)
+            if self.poison is None:
+                raw.fill_(float("nan"))
+                phred.fill_(float("nan"))
+        else:
+            row, kind, raw, phred = out
+            if min(t.numel() for t in out) < n or any(t.device != self.device for t in out):
+                raise ValueError("out buffers must hold n entries on the engine's device")
+        vs = snv.view() if snv is not None else None
+        vi = indel.view() if indel is not None else None
+        args = [self.ctx, ctypes.byref(vs) if vs is not None else None, ctypes.byref(vi) if vi is not None else None,
+                N.ptr(b.chrom), N.ptr(b.pos), N.ptr(b.allele_off), N.ptr(b.ref_len), N.ptr(b.alt_len), N.ptr(b.heap),
+                b.heap.numel(), n, N.ptr(row), N.ptr(kind), N.ptr(raw), N.ptr(phred), N.ptr(counters)]
+        if self.host_only:
+            N.check("avdb_cadd_match_host", self.lib.avdb_cadd_match_host(*args))
+        else:
+            N.check("avdb_cadd_match", self.lib.avdb_cadd_match(*args, self._stream()))
+        return row[:n], kind[:n], raw[:n], phred[:n]
 
     # -- formatting (host) ---------------------------------------------------
     def format_path(self, chrom_code: int, code: int) -> Optional[str]:

@@ -695,6 +695,96 @@ int avdb_keyset_probe_text(avdb_ctx* ctx, const void* table, size_t table_bytes,
                            const uint64_t* key_off, size_t n_keys, const uint8_t* q, const uint64_t* q_off,
                            const uint8_t* skip, size_t n, int32_t* match, uint64_t* counters, void* stream);
 
+/* ---- K10: CADD score annotation -------------------------------------------
+ * Replaces the per-variant tabix fetch of CADDUpdater.buffer_variant
+ * (Util/lib/python/loaders/cadd_updater.py:175-221, driven by
+ * Load/bin/load_cadd_scores.py) with a sort-merge join of a record batch against
+ * a CADD table held on the device.
+ * K10a, avdb_cadd_table_build: `text` is a slab of uncompressed CADD TSV ('#'
+ * header lines, then Chrom<TAB>Pos<TAB>Ref<TAB>Alt<TAB>RawScore<TAB>PHRED[<TAB>...],
+ * '\n'-separated, the last '\n' optional; n_lines as for K0: newlines + (text
+ * does not end in '\n'), avdb_vcf_count_lines counts them).  One row per data
+ * line (not empty, not '#'), in file order, into columns of n_lines entries each:
+ *   chrom    contig code; CADD's MT is the project's M; 255 unknown (never matches
+ *            on the device)
+ *   pos      1-based position
+ *   ref_off / ref_len / alt_off / alt_len   the alleles, as offsets into `text`
+ *            itself (the table keeps the slab; nothing is copied)
+ *   raw / phred   the scores: -?digits[.digits] of at most 15 significant and 22
+ *            fractional digits is parsed on the device to the double Python's
+ *            float() gives; any other text is flagged AVDB_CADD_ROW_SCORE_HOST and
+ *            left 0.0 for the caller to parse
+ *   flags    AVDB_CADD_ROW_*; a row with fewer than 6 fields or a POS that is not
+ *            a plain decimal in [1, 2^32) is AVDB_CADD_ROW_BAD and never matches
+ * first_row[c] / end_row[c] (u32[AVDB_CADD_N_CONTIGS]): the rows of contig c
+ * (first_row >= end_row: none).  counts (device, 4 x u64): AVDB_CADD_COUNT_*;
+ * an order violation is a contig whose rows are not one contiguous run, a pos
+ * that decreases inside a run, or more than 64 AVDB_CADD_ROW_BAD rows in a row —
+ * the order tabix requires; a table with violations must not be joined against.
+ * Workspace: avdb_cadd_workspace_size bytes, 256-byte aligned.
+ * K10b, avdb_cadd_match: per record (the arrays avdb_keyset_probe takes) the
+ * indel table is searched when ref_len > 1 or alt_len > 1, the SNV table
+ * otherwise (either may be NULL or empty); among the rows at the record's
+ * position the first, in file order, with
+ *   (ref == R || ref == A) && (alt == R || alt == A)     (R, A: the row's alleles)
+ * is the answer, exactly the reference's test (cadd_updater.py:202-204: a
+ * switched row matches).  row[i] = its index or -1; kind[i] = AVDB_CADD_*;
+ * raw[i] / phred[i] are written for matched records only.  counters (nullable,
+ * device, 3 x u64, added to): AVDB_CADD_CTR_*.
+ * The _host entries run the same per-line and per-record code in a loop on host
+ * memory, with a context from avdb_ctx_create(-1, ...). */
+#define AVDB_CADD_N_CONTIGS 25
+#define AVDB_CADD_ROW_SCORE_HOST 0x01u  /* a score the device does not parse: caller's float() */
+#define AVDB_CADD_ROW_BAD 0x02u         /* < 6 fields or POS not a plain decimal in [1, 2^32) */
+#define AVDB_CADD_NONE 0
+#define AVDB_CADD_SNV 1                 /* matched in the SNV table */
+#define AVDB_CADD_INDEL 2               /* matched in the indel table */
+#define AVDB_CADD_HOST 255              /* record contig 255: the caller resolves it by name */
+#define AVDB_CADD_COUNT_ROWS 0
+#define AVDB_CADD_COUNT_SCORE_HOST 1
+#define AVDB_CADD_COUNT_BAD 2
+#define AVDB_CADD_COUNT_ORDER_VIOLATIONS 3
+#define AVDB_CADD_N_COUNTS 4
+#define AVDB_CADD_CTR_SNV 0
+#define AVDB_CADD_CTR_INDEL 1
+#define AVDB_CADD_CTR_NOT_MATCHED 2
+#define AVDB_CADD_N_CTRS 3
+typedef struct avdb_cadd_table {
+  uint32_t struct_size;     /* sizeof(avdb_cadd_table) */
+  uint32_t reserved;
+  uint64_t n_rows;          /* 0: an empty table (the pointers are not read) */
+  const uint8_t* text;      /* the slab the table was built from */
+  uint64_t text_bytes;
+  const uint8_t* chrom;
+  const uint32_t* pos;
+  const uint64_t* ref_off;
+  const uint32_t* ref_len;
+  const uint64_t* alt_off;
+  const uint32_t* alt_len;
+  const double* raw;
+  const double* phred;
+  const uint8_t* flags;
+  const uint32_t* first_row;
+  const uint32_t* end_row;
+} avdb_cadd_table;
+int avdb_cadd_workspace_size(size_t text_bytes, size_t n_lines, size_t* bytes);
+int avdb_cadd_table_build(avdb_ctx* ctx, const uint8_t* text, size_t text_bytes, size_t n_lines, uint8_t* chrom,
+                          uint32_t* pos, uint64_t* ref_off, uint32_t* ref_len, uint64_t* alt_off, uint32_t* alt_len,
+                          double* raw, double* phred, uint8_t* flags, uint32_t* first_row, uint32_t* end_row,
+                          uint64_t* counts, void* workspace, size_t workspace_bytes, void* stream);
+int avdb_cadd_match(avdb_ctx* ctx, const avdb_cadd_table* snv, const avdb_cadd_table* indel, const uint8_t* chrom,
+                    const uint32_t* pos, const uint64_t* allele_off, const uint32_t* ref_len, const uint32_t* alt_len,
+                    const uint8_t* heap, size_t heap_bytes, size_t n, int32_t* row, uint8_t* kind, double* raw,
+                    double* phred, uint64_t* counters, void* stream);
+int avdb_cadd_table_build_host(const avdb_ctx* ctx, const uint8_t* text, size_t text_bytes, size_t n_lines,
+                               uint8_t* chrom, uint32_t* pos, uint64_t* ref_off, uint32_t* ref_len, uint64_t* alt_off,
+                               uint32_t* alt_len, double* raw, double* phred, uint8_t* flags, uint32_t* first_row,
+                               uint32_t* end_row, uint64_t* counts);
+int avdb_cadd_match_host(const avdb_ctx* ctx, const avdb_cadd_table* snv, const avdb_cadd_table* indel,
+                         const uint8_t* chrom, const uint32_t* pos, const uint64_t* allele_off,
+                         const uint32_t* ref_len, const uint32_t* alt_len, const uint8_t* heap, size_t heap_bytes,
+                         size_t n, int32_t* row, uint8_t* kind, double* raw, double* phred, uint64_t* counters);
+
 /* ---- K9: genome-piece sharding of VCF text --------------------------------
  * The reference runs one process per chromosome file (Load/bin/load_vcf_file.py:
  * 307-313).  One file is split over the ranks of a node by a piece plan
