@@ -11,8 +11,9 @@ namespace cadd {
 
 constexpr uint32_t kContigs = AVDB_CADD_N_CONTIGS;
 constexpr uint32_t kUnknown = 255;
-// how far the index pass looks past AVDB_CADD_ROW_BAD rows for a row's neighbour
-// (a longer run of unparsable rows is an order violation: the table is not usable)
+// the longest run of AVDB_CADD_ROW_BAD rows the index pass looks across for a row's
+// neighbour: the kBadRun + 1 rows on either side are examined (a longer run of
+// unparsable rows is an order violation: the table is not usable)
 constexpr uint32_t kBadRun = 64;
 
 struct Cols {  // the table's columns as the build writes them
@@ -182,7 +183,7 @@ AVDB_HD IndexEvent index_row(const uint8_t* chrom, uint32_t* pos, const uint8_t*
   IndexEvent ev{kUnknown, false, false, false};
   uint64_t p = i;  // nearest good row before i (i: none)
   bool lost = false;
-  for (uint32_t k = 0; p == i && k < kBadRun && k < i; ++k)
+  for (uint32_t k = 0; p == i && k <= kBadRun && k < i; ++k)
     if (!(flags[i - 1 - k] & AVDB_CADD_ROW_BAD)) p = i - 1 - k;
   if (p == i && i > kBadRun) lost = true;
   if (flags[i] & AVDB_CADD_ROW_BAD) {
@@ -191,7 +192,7 @@ AVDB_HD IndexEvent index_row(const uint8_t* chrom, uint32_t* pos, const uint8_t*
     return ev;
   }
   uint64_t q = n;  // nearest good row after i (n: none)
-  for (uint32_t k = 0; q == n && k < kBadRun && i + 1 + k < n; ++k)
+  for (uint32_t k = 0; q == n && k <= kBadRun && i + 1 + k < n; ++k)
     if (!(flags[i + 1 + k] & AVDB_CADD_ROW_BAD)) q = i + 1 + k;
   const uint32_t c = chrom[i];
   ev.violation = lost;

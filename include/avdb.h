@@ -716,6 +716,9 @@ int avdb_keyset_probe_text(avdb_ctx* ctx, const void* table, size_t table_bytes,
  *            left 0.0 for the caller to parse
  *   flags    AVDB_CADD_ROW_*; a row with fewer than 6 fields or a POS that is not
  *            a plain decimal in [1, 2^32) is AVDB_CADD_ROW_BAD and never matches
+ *            (chrom 255, both allele offsets the line's own, lengths and scores 0;
+ *            pos: that of the nearest earlier row that is not BAD when at most 64
+ *            BAD rows lie between, else 0)
  * first_row[c] / end_row[c] (u32[AVDB_CADD_N_CONTIGS]): the rows of contig c
  * (first_row >= end_row: none).  counts (device, 4 x u64): AVDB_CADD_COUNT_*;
  * an order violation is a contig whose rows are not one contiguous run, a pos

@@ -216,3 +216,116 @@ def test_t4_argument_checks(host, tables):
     u = CADDUpdater(None, None, host)
     assert u.match_batch(["1:100:A:C"])[1].tolist() == [N.CADD_NONE] and u.match_batch([])[0].size == 0
     assert torch.equal(host.new_cadd_counters(), torch.zeros(3, dtype=torch.int64))
+
+
+# ---- the header's restatement (cadd_common.expect_table / expect_match) ----------
+def _check_table(host, text, what):
+    want = C.expect_table(text)
+    C.assert_same_table(C.table_columns(host.cadd_table_build(text)), want, what)
+    return want
+
+
+def _window_slab_and_odd():
+    import test_gpu_cadd as G
+    odd = HEADER + b"1\t5\tA\tC\t1e-05\t1.5\n1\t6\tA\n\n1\tx\tA\tC\t1\t1\n1\t7\tAT\tA\t-0.000000\t.5\r\n" \
+                   b"GL1\t7\tA\tC\t1\t2\n2\t9\tA\tC\t1\t2\n1\t9\tA\tC\t1234567890.123456\t2\n2\t8\tA\tC\t1\t2"
+    return G.window_slab(), odd
+
+
+def test_t5_expect_table_equals_the_host_entry(host):
+    """expect_table is written from avdb.h, not from avdb_cadd.hpp: every column
+    (doubles as bits) and all four counts, on the suite's texts and a seeded fuzz."""
+    snv, indel, _, _ = C.golden()
+    slab, odd = _window_slab_and_odd()
+    for what, text in (("snv", snv), ("indel", indel), ("window_slab", slab), ("odd", odd), ("empty", b""),
+                       ("header", HEADER), ("blank", b"\n\n")):
+        _check_table(host, text, what)
+    cols, counts = C.expect_table(odd)
+    assert counts == [8, 3, 2, 2] and cols["pos"].tolist() == [5, 5, 5, 7, 7, 9, 9, 8]
+    rng = random.Random(2024)
+    seen = [0, 0, 0, 0]
+    for k in range(400):
+        text = C.fuzz_table(rng)
+        _, counts = _check_table(host, text, "fuzz %d: %r" % (k, text))
+        seen = [a + (b > 0) for a, b in zip(seen, counts)]
+    assert min(seen) >= 100  # the fuzz reaches rows, host-left scores, BAD rows and violations
+
+
+def test_t5_a_long_allele_and_long_lines(host):
+    rng = random.Random(5)
+    big = "".join(rng.choice("ACGT") for _ in range(24000)).encode()
+    text = b"1\t5\tA\tC\t0.5\t1.5\n1\t6\tA\t" + big + b"\t0.25\t2.5\textra\n1\t7\t" + big + b"\tA\t1\t2"
+    cols, counts = _check_table(host, text, "24 kB allele")
+    assert counts == [3, 0, 0, 0] and cols["alt_len"].tolist() == [1, 24000, 1]
+
+
+BAD = b"1\tx\tA\tC\t1\t1\n"
+
+
+def _bad_run_texts(n):
+    g = lambda c, p: b"%d\t%d\tA\tC\t0.5\t1.5\n" % (c, p)
+    return {"top": BAD * n + g(1, 5) + g(1, 6),
+            "mid": g(1, 5) + g(1, 6) + BAD * n + g(1, 7) + g(1, 8),
+            "mid, pos decreases": g(1, 5) + g(1, 6) + BAD * n + g(1, 4),
+            "boundary": g(1, 5) + g(1, 6) + BAD * n + g(2, 1) + g(2, 2),
+            "end": g(1, 5) + g(1, 6) + BAD * n,
+            "end, no newline": (g(1, 5) + g(1, 6) + BAD * n)[:-1],
+            "far down": g(3, 1) * 100 + g(1, 6) + BAD * n + g(1, 7)}
+
+
+@pytest.mark.parametrize("n", [63, 64, 65, 200])
+def test_t5_bad_runs_at_the_bound(host, n):
+    """avdb.h: *more than* 64 BAD rows in a row are a violation, wherever they stand."""
+    texts = _bad_run_texts(n)
+    got = {}
+    for what, text in texts.items():
+        cols, counts = _check_table(host, HEADER + text, "%d BAD rows, %s" % (n, what))
+        assert counts[0] == text.count(b"\n") + (not text.endswith(b"\n")) and counts[2] == n
+        got[what] = (cols, counts[3])
+    if n <= 64:
+        assert [v for _, v in got.values()] == [0, 0, 1, 0, 0, 0, 0]
+        cols = got["mid"][0]
+        assert cols["first_row"][0] == 0 and cols["end_row"][0] == n + 4  # one run: the row after is no start
+        assert cols["pos"].tolist() == [5] + [6] * (n + 1) + [7, 8]
+        assert got["top"][0]["pos"].tolist() == [0] * n + [5, 6]
+        cols = got["boundary"][0]
+        assert (cols["first_row"][:2].tolist(), cols["end_row"][:2].tolist()) == ([0, n + 2], [2, n + 4])
+    else:
+        assert all(v > 0 for what, (_, v) in got.items() if not what.startswith("end")), got
+        assert got["top"][1] == n - 64  # rows 65 .. n see no usable row among the 65 before them
+        assert got["end"][1] == n - 65
+        # the 65th BAD row of the run still reaches the good row 65 rows up; the 66th does not
+        assert got["mid"][0]["pos"][2:2 + n].tolist() == [6] * 65 + [0] * (n - 65)
+        with pytest.raises(ValueError):
+            CaddTable.from_text(HEADER + texts["mid"], host)
+    if n == 64:
+        assert len(CaddTable.from_text(HEADER + texts["mid"], host)) == 68
+
+
+def test_t6_expect_match_equals_the_host_join(host):
+    snv, indel, recs, _ = C.golden()
+    ids = [r["metaseq_id"] for r in recs]
+    want = C.expect_arrays(snv, indel, ids)
+    for a, b in zip(C.expect_match(snv, indel, ids), want):  # the two restatements agree where both apply
+        assert np.array_equal(C.bits(a), C.bits(b)) if a.dtype == np.float64 else np.array_equal(a, b)
+    rng = random.Random(77)
+    kinds, hits, n = set(), 0, 0
+    for k in range(120):
+        s, i, ids = C.join_case(rng, edge=k % 4 == 0)
+        erow, ekind = C.check_join(host, s, i, ids, "case %d" % k)
+        kinds |= set(ekind.tolist())
+        hits += int((erow >= 0).sum())
+        n += len(ids)
+    assert kinds == {N.CADD_NONE, N.CADD_SNV, N.CADD_INDEL, N.CADD_HOST} and hits > n // 5 and n > 20000
+
+
+def test_t6_join_edges_by_hand(host):
+    """The cases the fuzz is built around, with the answers written out."""
+    P = 2 ** 32 - 1
+    snv = HEADER + b"1\t2147483648\tA\tC\t0.5\t1.5\n1\t2147483648\tA\t1\n1\t2147483648x\tG\tT\t9\t9\n" \
+                   b"1\t2147483648\tG\tT\t0.25\t2.5\n1\t%d\tA\tA\t1.5\t3.5\n2\t%d\tC\tG\t2.5\t4.5\n" % (P, P)
+    ids = ["1:2147483648:A:C", "1:2147483648:T:G", "1:2147483648::", "1:%d:A:A" % P, "1:%d:C:G" % P, "2:%d:G:C" % P,
+           "1:2147483647:A:C", "1:0:A:C", "3:%d:C:G" % P, "GL1:5:A:C"]
+    erow, ekind = C.check_join(host, snv, HEADER, ids, "by hand")
+    assert erow.tolist() == [0, 3, -1, 4, -1, 5, -1, -1, -1, -1]
+    assert ekind.tolist() == [1, 1, 0, 1, 0, 1, 0, 0, 0, N.CADD_HOST]
