@@ -28,6 +28,7 @@ AVDB_EHIP = -2
 AVDB_ENOMEM = -3
 AVDB_ERANGE = -4
 AVDB_ERCCL = -5
+AVDB_ENOTBGZF = -6
 RCCL_ID_BYTES = 128
 
 STATUS_OK = 0
@@ -63,6 +64,13 @@ CADD_NONE, CADD_SNV, CADD_INDEL, CADD_HOST = 0, 1, 2, 255
 CADD_COUNT_ROWS, CADD_COUNT_SCORE_HOST, CADD_COUNT_BAD, CADD_COUNT_ORDER_VIOLATIONS, CADD_N_COUNTS = 0, 1, 2, 3, 4
 CADD_CTR_SNV, CADD_CTR_INDEL, CADD_CTR_NOT_MATCHED, CADD_N_CTRS = 0, 1, 2, 3
 MAX_ALG_ID = 64
+BGZF_STATUS = ("OK", "bad header", "input overrun", "bad block type", "bad stored length", "bad code lengths",
+               "bad symbol", "distance before block start", "output longer than ISIZE", "output shorter than ISIZE",
+               "CRC mismatch")  # AVDB_BGZF_* (include/avdb.h), by code
+(BGZF_OK, BGZF_BAD_HEADER, BGZF_OVERRUN, BGZF_BAD_BTYPE, BGZF_BAD_STORED, BGZF_BAD_LENS, BGZF_BAD_SYMBOL,
+ BGZF_DIST_FAR, BGZF_OUT_LONG, BGZF_OUT_SHORT, BGZF_BAD_CRC) = range(11)
+BGZF_COUNT_OK, BGZF_COUNT_FAILED, BGZF_COUNT_FIRST_FAILED, BGZF_N_COUNTS = 0, 1, 2, 3
+BGZF_MAX_OUT = 65536  # ISIZE of a member is at most this
 
 
 class FormatOpts(ctypes.Structure):
@@ -126,6 +134,7 @@ EXPORTED_SYMBOLS = [
     "avdb_hist_allgather_workspace_size", "avdb_hist_allgather",
     "avdb_cadd_workspace_size", "avdb_cadd_table_build", "avdb_cadd_match",
     "avdb_cadd_table_build_host", "avdb_cadd_match_host",
+    "avdb_bgzf_index_host", "avdb_bgzf_inflate", "avdb_bgzf_inflate_host",
 ]
 
 
@@ -133,7 +142,7 @@ SMALL_PATH, SMALL_KEY, SMALL_DISPLAY = 1, 2, 4
 KEYS_TOTALS_READY = 1  # AVDB_KEYS_TOTALS_READY
 KEYS_DIGEST_DEFERRED = 2  # AVDB_KEYS_DIGEST_DEFERRED
 KEYS_OFF32 = 4  # AVDB_KEYS_OFF32 (narrow key / path offsets)
-OPT_K4_GRID, OPT_K7_GRID = 1, 2  # avdb_ctx_set_option
+OPT_K4_GRID, OPT_K7_GRID, OPT_K11_GRID = 1, 2, 3  # avdb_ctx_set_option
 KEYED_TOTALS, KEYED_LONG_CODES, KEYED_DEDUP_MARKS = 1, 2, 4  # avdb_record_prep_keyed's *totals_written bits
 DEDUP_MARKED = 1  # AVDB_DEDUP_MARKED
 DEDUP_ONEPASS = 2  # AVDB_DEDUP_ONEPASS (marks from avdb_keyed_prep)
@@ -253,6 +262,10 @@ def _sig(lib):
     f.avdb_cadd_match_host.argtypes = [P, ctypes.POINTER(CaddTableView), ctypes.POINTER(CaddTableView), P, P, P, P, P,
                                        P, SZ, SZ, P, P, P, P, P]
     f.avdb_cadd_match.argtypes = f.avdb_cadd_match_host.argtypes + [P]
+    f.avdb_bgzf_index_host.argtypes = [P, SZ, SZ, P, P, ctypes.POINTER(SZ), ctypes.POINTER(SZ),
+                                       ctypes.POINTER(ctypes.c_uint64)]
+    f.avdb_bgzf_inflate_host.argtypes = [P, P, SZ, P, P, SZ, P, SZ, P, P]
+    f.avdb_bgzf_inflate.argtypes = f.avdb_bgzf_inflate_host.argtypes + [P]
     for name in EXPORTED_SYMBOLS:
         if name not in ("avdb_last_error",):
             getattr(f, name).restype = I32

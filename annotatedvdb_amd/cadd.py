@@ -11,10 +11,13 @@ when ``len(ref) > 1 or len(alt) > 1`` else the SNV table (``:189``), the first r
 at the position, in file order, with ``ref in [R, A] and alt in [R, A]``
 (``:202-204`` — deliberately that loose: a switched row matches).
 
-bgzip files are multi-member gzip, so Python's ``gzip`` reads them; tabix indexes
-are not read.  A whole-genome SNV file does not fit in HBM:
-``CaddTable.from_file(path, contigs=[...])`` keeps one chromosome's lines while it
-reads, the way the reference's loop runs per chromosome.
+A bgzip file read whole (``CaddTable.from_file(path)``) is inflated on the GPU (K11,
+``bgzf.BgzfFile``) and the text handed to the table build where it lies: no host
+copy of the text exists.  Tabix indexes are not read.  A whole-genome SNV file does
+not fit in HBM: ``CaddTable.from_file(path, contigs=[...])`` keeps one chromosome's
+lines while it reads, the way the reference's loop runs per chromosome; that filter
+runs on the host, where bgzip files are multi-member gzip, so Python's ``gzip`` reads
+them.
 
 What stays with the caller, as in the reference it needs a database: the lookup
 of a variant's primary key by metaseq id (``__get_variant_primary_key`` →
@@ -83,6 +86,14 @@ class CaddTable(object):
         """A plain, gzip or bgzip CADD TSV.  ``contigs``: keep only the lines of
         these contigs (CADD labels: ``'1'`` .. ``'22'``, ``'X'``, ``'Y'``, ``'MT'``; ``'M'``
         and a ``chr`` prefix are accepted) while reading."""
+        from . import bgzf
+        if contigs is None and bgzf.is_bgzf(path):
+            from .engine import default_engine
+            engine = engine or default_engine()
+            try:
+                return cls(engine.cadd_table_build(bgzf.BgzfFile(path, engine).read()), engine)
+            except bgzf.NotBgzf:
+                pass
         with open(path, "rb") as fh:
             magic = fh.read(2)
         opener = gzip.open if magic == b"\x1f\x8b" else open

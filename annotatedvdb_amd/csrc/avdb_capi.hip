@@ -99,6 +99,9 @@ extern "C" int avdb_ctx_create(int device, const uint32_t* chrom_len, int n_chro
   }
   c->k4_grid = 0;  // avdb_ctx_set_option(AVDB_OPT_K4_GRID): workgroups, 0 = n_cu * k4_blocks_per_cu
   c->k7_grid = 0;  // avdb_ctx_set_option(AVDB_OPT_K7_GRID): workgroups, 0 = the compiled grid
+  c->k11_grid = 0;  // avdb_ctx_set_option(AVDB_OPT_K11_GRID): workgroups, 0 = sixteen per CU
+  c->k11_windows = nullptr;
+  c->k11_windows_n = 0;
   c->k7_raw_blocks = 256;
   if (const char* s = getenv("AVDB_K7_RAW_BLOCKS")) c->k7_raw_blocks = size_t(strtoull(s, nullptr, 10));
   *out = c;
@@ -122,6 +125,13 @@ extern "C" int avdb_ctx_set_option(avdb_ctx* ctx, int option, int64_t value) {
       }
       ctx->k7_grid = int(value);
       return AVDB_OK;
+    case AVDB_OPT_K11_GRID:
+      if (value < 0 || value > 16384) {  // (each workgroup has a 64 KiB window in the context's workspace)
+        avdb_set_error("avdb_ctx_set_option: K11 grid of %lld workgroups out of range", (long long)value);
+        return AVDB_EINVAL;
+      }
+      ctx->k11_grid = int(value);
+      return AVDB_OK;
     default:
       avdb_set_error("avdb_ctx_set_option: unknown option %d", option);
       return AVDB_EINVAL;
@@ -133,6 +143,10 @@ extern "C" int avdb_ctx_destroy(avdb_ctx* ctx) {
   if (ctx->d_seq_digest) {
     (void)hipSetDevice(ctx->device);
     (void)hipFree(ctx->d_seq_digest);
+  }
+  if (ctx->k11_windows) {
+    (void)hipSetDevice(ctx->device);
+    (void)hipFree(ctx->k11_windows);
   }
   if (ctx->d_loc_tail) {
     (void)hipSetDevice(ctx->device);

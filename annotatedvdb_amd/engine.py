@@ -1414,6 +1414,111 @@ class Engine:
             N.check("avdb_cadd_match", self.lib.avdb_cadd_match(*args, self._stream()))
         return row[:n], kind[:n], raw[:n], phred[:n]
 
+    # -- K11: BGZF input ---------------------------------------------------------
+    @staticmethod
+    def _host_u8(data) -> np.ndarray:
+        """``data`` (bytes-like, numpy ``uint8`` or a ``uint8`` tensor) as a contiguous host array, without a copy
+        where it already is one."""
+        if isinstance(data, torch.Tensor):
+            if data.dtype != torch.uint8 or data.dim() != 1:
+                raise TypeError("compressed data must be a 1-d uint8 tensor")
+            return data.detach().cpu().contiguous().numpy()
+        if isinstance(data, np.ndarray):
+            if data.dtype != np.uint8 or data.ndim != 1:
+                raise TypeError("compressed data must be a 1-d uint8 array")
+            return np.ascontiguousarray(data)
+        return np.frombuffer(data, dtype=np.uint8)
+
+    def bgzf_index(self, data) -> "BgzfIndex":
+        """``avdb_bgzf_index_host`` over the complete BGZF members at the head of
+        ``data`` (host memory): see :class:`annotatedvdb_amd.bgzf.BgzfIndex`.  Raises
+        ``bgzf.NotBgzf`` when the first member is gzip but not BGZF, ``bgzf.BgzfError``
+        for a malformed member later in the chain."""
+        from .bgzf import BgzfError, BgzfIndex, NotBgzf
+        a = self._host_u8(data)
+        nb = a.size
+        ins, outs, at, total = [], [], 0, 0
+        cap = max(16, min(nb // 26 + 1, 1 << 20))
+        n, consumed, out_bytes = ctypes.c_size_t(), ctypes.c_size_t(), ctypes.c_uint64()
+        while True:
+            in_off, out_off = np.empty(cap, dtype=np.uint64), np.empty(cap + 1, dtype=np.uint64)
+            rc = self.lib.avdb_bgzf_index_host(a.ctypes.data + at if nb else None, nb - at, cap, in_off.ctypes.data,
+                                               out_off.ctypes.data, ctypes.byref(n), ctypes.byref(consumed),
+                                               ctypes.byref(out_bytes))
+            if rc == N.AVDB_ENOTBGZF and at == 0:
+                raise NotBgzf(N.last_error())
+            if rc < 0:
+                raise BgzfError("%s (the chain examined starts at offset %d)" % (N.last_error(), at))
+            k = int(n.value)
+            ins.append(in_off[:k] + np.uint64(at))
+            outs.append(out_off[:k] + np.uint64(total))
+            at += int(consumed.value)
+            total += int(out_bytes.value)
+            if k < cap:
+                break
+        outs.append(np.array([total], dtype=np.uint64))
+        return BgzfIndex(np.concatenate(ins), np.concatenate(outs), at, total)
+
+    def bgzf_inflate(self, data, index: Optional["BgzfIndex"] = None, raise_on_error: bool = True):
+        """K11: the text of the BGZF members of ``data`` (bytes-like, numpy ``uint8`` or a
+        ``uint8`` tensor; with ``index`` it may already be on the device) as a ``uint8``
+        tensor on this engine's device: compressed bytes go up, the text stays in HBM.
+        Without ``index`` every byte of ``data`` must belong to a complete member.  A
+        member that fails (``N.BGZF_*``) raises ``bgzf.BgzfError``; with
+        ``raise_on_error=False`` the call returns ``(text, status uint8[n_blocks],
+        counts)`` instead, the ranges of failed members left as allocated.  On a
+        host-only engine the library's host entry runs the same per-member code."""
+        from .bgzf import BgzfError
+        if index is None:
+            host = self._host_u8(data)
+            index = self.bgzf_index(host)
+            if index.consumed != host.size:
+                raise BgzfError("truncated BGZF data: %d bytes after the last complete member (offset %d)"
+                                % (host.size - index.consumed, index.consumed))
+            data = host
+        if isinstance(data, torch.Tensor):
+            comp = data
+        else:
+            a = self._host_u8(data)
+            if not a.flags.writeable:  # (bytes: torch warns about a view nobody writes through)
+                a = a.copy()
+            comp = torch.from_numpy(a)
+        if comp.dtype != torch.uint8 or comp.dim() != 1:
+            raise TypeError("compressed data must be a 1-d uint8 tensor")
+        comp = comp.to(self.device, non_blocking=True) if comp.device != self.device else comp
+        if not comp.is_contiguous():
+            comp = comp.contiguous()
+        n, nb, total = index.n_blocks, comp.numel(), index.out_bytes
+        in_off, out_off = np.ascontiguousarray(index.in_off, dtype=np.uint64), \
+            np.ascontiguousarray(index.out_off, dtype=np.uint64)
+        # sizes are checked here, before the call (the decoder checks them again per member)
+        if in_off.size != n or out_off.size != n + 1:
+            raise ValueError("index arrays must hold n_blocks and n_blocks + 1 entries")
+        if n:
+            sizes = np.diff(out_off.astype(np.int64))
+            if int(out_off[0]) != 0 or int(out_off[-1]) != total or (sizes < 0).any() or (sizes > N.BGZF_MAX_OUT).any():
+                raise ValueError("index out_off is not the exclusive sum of member sizes of at most 65536")
+            if (np.diff(in_off.astype(np.int64)) < 26).any() or int(in_off[-1]) + 26 > nb:
+                raise ValueError("index in_off does not lie inside the compressed data")
+        out = self.empty(max(1, total), torch.uint8)
+        status = self.empty(max(1, n), torch.uint8)
+        counts = self.empty(N.BGZF_N_COUNTS, torch.int64)
+        d_in = torch.from_numpy(in_off.view(np.int64)).to(self.device, non_blocking=True)
+        d_out = torch.from_numpy(out_off.view(np.int64)).to(self.device, non_blocking=True)
+        args = [self.ctx, N.ptr(comp) if nb else None, nb, N.ptr(d_in) if n else None, N.ptr(d_out), n, N.ptr(out),
+                total, N.ptr(status), N.ptr(counts)]
+        if self.host_only:
+            N.check("avdb_bgzf_inflate_host", self.lib.avdb_bgzf_inflate_host(*args))
+        else:
+            N.check("avdb_bgzf_inflate", self.lib.avdb_bgzf_inflate(*args, self._stream()))
+        cnt = counts.cpu().numpy().astype(np.uint64)  # (the sync: comp, d_in and d_out are done with)
+        if not raise_on_error:
+            return out[:total], status[:n], cnt
+        if int(cnt[N.BGZF_COUNT_FAILED]):
+            k = int(cnt[N.BGZF_COUNT_FIRST_FAILED])
+            raise BgzfError.for_block(k, int(in_off[k]), int(status[k]), int(cnt[N.BGZF_COUNT_FAILED]))
+        return out[:total]
+
     # -- formatting (host) ---------------------------------------------------
     def format_path(self, chrom_code: int, code: int) -> Optional[str]:
         buf = ctypes.create_string_buffer(N.MAX_PATH)

@@ -90,16 +90,49 @@ def assign_files(files: List[str], world: int) -> List[List[str]]:
     return out
 
 
-def read_text(path: str) -> bytes:
+def _bgzf_file(path: str, engine):
+    """``path`` as a :class:`bgzf.BgzfFile` when it is a bgzip file (K11 inflates it on
+    the GPU), else None: a plain single-member gzip file stays on Python's ``gzip``."""
+    from . import bgzf
+    if path.endswith(".gz") and bgzf.is_bgzf(path):
+        return bgzf.BgzfFile(path, engine)
+    return None
+
+
+def read_text(path: str, engine=None) -> bytes:
+    from .bgzf import NotBgzf
+    bf = _bgzf_file(path, engine)
+    if bf is not None:
+        try:
+            return bf.read().cpu().numpy().tobytes()
+        except NotBgzf:
+            pass
     opener = gzip.open if path.endswith(".gz") else open
     with opener(path, "rb") as fh:
         return fh.read()
 
 
-def iter_batches(path: str, batch_bytes: int):
+def iter_batches(path: str, batch_bytes: int, engine=None):
     """The file as consecutive blocks of about ``batch_bytes`` cut after a newline
     (a line longer than a block stays whole): host memory stays bounded by the
-    batch, whatever the file size (gzip streams too)."""
+    batch, whatever the file size (gzip streams too).  A bgzip file is inflated on
+    ``engine``'s GPU (K11), a quarter of ``batch_bytes`` of compressed bytes at a time
+    (dbSNP text at bgzip's level 6 is about four times its compressed size), and each
+    block is copied back once, since ``load_vcf_text`` takes ``bytes``."""
+    from .bgzf import NotBgzf
+    bf = _bgzf_file(path, engine)
+    if bf is not None:
+        pieces = bf.iter_text(max(1, batch_bytes // 4))
+        try:
+            first = next(pieces, None)
+        except NotBgzf:
+            bf = None
+        if bf is not None:
+            if first is not None:
+                yield first.cpu().numpy().tobytes()
+            for piece in pieces:
+                yield piece.cpu().numpy().tobytes()
+            return
     opener = gzip.open if path.endswith(".gz") else open
     with opener(path, "rb") as fh:
         carry = b""
@@ -152,7 +185,7 @@ def load(path: str, args, loader, rank: int, plan=None) -> Dict[str, int]:
     before = {k: loader.get_count(k) for k in COUNTERS}
     t0 = time.perf_counter()
     with open(base + ".r%d.mapping" % rank, "w") as mfh, open(base + ".r%d.copy" % rank, "w") as cfh:
-        for block in iter_batches(path, args.batchBytes):
+        for block in iter_batches(path, args.batchBytes, loader._engine):
             if plan is not None:
                 block = rank_text(block, loader, plan, rank)
                 if not block:

@@ -62,6 +62,7 @@ extern "C" {
 #define AVDB_ENOMEM (-3)
 #define AVDB_ERANGE (-4)   /* output buffer too small */
 #define AVDB_ERCCL (-5)    /* RCCL could not be loaded, or a collective failed */
+#define AVDB_ENOTBGZF (-6) /* avdb_bgzf_index_host: the first member is gzip, but not BGZF */
 
 /* per-record status (u8) */
 #define AVDB_STATUS_OK 0
@@ -113,6 +114,9 @@ int avdb_ctx_destroy(avdb_ctx* ctx);
 /*   AVDB_OPT_K7_GRID  workgroups (one wave each) of K7's write pass, 0 = the default; a
  *                     persistent grid below the chip's occupancy leaves registers to K4 */
 #define AVDB_OPT_K7_GRID 2
+/*   AVDB_OPT_K11_GRID workgroups (one wave each) of K11's inflate grid, 0 = sixteen per CU; at most
+ *                     16384; fewer make each stride over more members */
+#define AVDB_OPT_K11_GRID 3
 int avdb_ctx_set_option(avdb_ctx* ctx, int option, int64_t value);
 int avdb_ctx_n_chrom(const avdb_ctx* ctx);
 /* GA4GH refget digests (32 chars each, no "ga4gh:SQ." prefix) of every contig,
@@ -787,6 +791,62 @@ int avdb_cadd_match_host(const avdb_ctx* ctx, const avdb_cadd_table* snv, const 
                          const uint8_t* chrom, const uint32_t* pos, const uint64_t* allele_off,
                          const uint32_t* ref_len, const uint32_t* alt_len, const uint8_t* heap, size_t heap_bytes,
                          size_t n, int32_t* row, uint8_t* kind, double* raw, double* phred, uint64_t* counters);
+
+/* ---- K11: BGZF (bgzip) input inflated on the GPU ------------------------------
+ * The files the reference loads arrive as bgzip (.vcf.gz, CADD's .tsv.gz with a .tbi):
+ * a chain of independent gzip members (SAM specification 4.1), each of at most 64 KiB
+ * of output, each stating its compressed size (BSIZE in the 'BC' extra subfield) and
+ * its output size (ISIZE in the trailer).
+ *
+ * avdb_bgzf_index_host walks the members of data[0 .. bytes) (host memory).  A member
+ * carries magic 1f 8b, CM 8, FLG 4 (FEXTRA), a 'BC' subfield of length 2 (other extra
+ * subfields before or after it are skipped), BSIZE + 1 >= its header and trailer, and
+ * ISIZE <= 65536.  in_off[k] (blocks_cap entries) is the offset of member k, out_off[k]
+ * (blocks_cap + 1 entries) the exclusive sum of ISIZE, out_off[*n_blocks] = *out_bytes;
+ * *consumed is the offset after the last complete member.  The walk stops without error
+ * at a member that runs past `bytes` (a caller streaming a file carries the tail over)
+ * and after blocks_cap members (call again from *consumed).  AVDB_ENOTBGZF: the first
+ * member is gzip (magic, CM 8) but no BGZF member; AVDB_EINVAL: no gzip magic there, or
+ * a malformed member later in the chain (avdb_last_error names its offset).
+ *
+ * avdb_bgzf_inflate (device pointers; avdb_bgzf_inflate_host: the same per-member code
+ * on host pointers, on an avdb_ctx_create(-1, ...) context) writes member k's bytes to
+ * out[out_off[k] .. out_off[k+1]) and its AVDB_BGZF_* code to status[k] (n_blocks
+ * entries; out_off has n_blocks + 1).  Full RFC 1951 (stored, fixed and dynamic blocks,
+ * any number per member), code sets accepted as zlib's inflate_table accepts them
+ * (over-subscribed: refused; incomplete: refused unless a single code of length 1;
+ * no end-of-block code, more than 286 literal/length or 30 distance codes: refused),
+ * and the CRC-32 of the output checked against the trailer.  For any input bytes the
+ * decoder reads only comp[0 .. comp_bytes) (a member: only its own extent) and writes
+ * only the ranges of members whose status is AVDB_BGZF_OK: a member that fails writes
+ * nothing.  counts[AVDB_BGZF_N_COUNTS] (set by the call): members OK, members failed,
+ * index of the first failed member (~0 when none).  The device entry decodes each member
+ * in a 64 KiB window of a workspace the context owns (allocated at the first call, one
+ * window per workgroup of the grid, freed by avdb_ctx_destroy). */
+#define AVDB_BGZF_OK 0
+#define AVDB_BGZF_BAD_HEADER 1  /* no BGZF member at in_off[k], ISIZE != out_off[k+1] - out_off[k], a range outside
+                                   comp / out, or a deflate stream that ends before the trailer */
+#define AVDB_BGZF_OVERRUN 2     /* the deflate stream runs past the member's compressed extent */
+#define AVDB_BGZF_BAD_BTYPE 3   /* block type 3 */
+#define AVDB_BGZF_BAD_STORED 4  /* stored block: LEN != ~NLEN */
+#define AVDB_BGZF_BAD_LENS 5    /* a code-length set zlib refuses */
+#define AVDB_BGZF_BAD_SYMBOL 6  /* bits that are no code of the set, or literal/length 286-287, distance 30-31 */
+#define AVDB_BGZF_DIST_FAR 7    /* a distance before the member's first byte */
+#define AVDB_BGZF_OUT_LONG 8    /* more output than ISIZE */
+#define AVDB_BGZF_OUT_SHORT 9   /* less output than ISIZE */
+#define AVDB_BGZF_BAD_CRC 10    /* CRC-32 of the output != the trailer's */
+#define AVDB_BGZF_COUNT_OK 0
+#define AVDB_BGZF_COUNT_FAILED 1
+#define AVDB_BGZF_COUNT_FIRST_FAILED 2
+#define AVDB_BGZF_N_COUNTS 3
+int avdb_bgzf_index_host(const uint8_t* data, size_t bytes, size_t blocks_cap, uint64_t* in_off, uint64_t* out_off,
+                         size_t* n_blocks, size_t* consumed, uint64_t* out_bytes);
+int avdb_bgzf_inflate(avdb_ctx* ctx, const uint8_t* comp, size_t comp_bytes, const uint64_t* in_off,
+                      const uint64_t* out_off, size_t n_blocks, uint8_t* out, size_t out_cap, uint8_t* status,
+                      uint64_t* counts, void* stream);
+int avdb_bgzf_inflate_host(const avdb_ctx* ctx, const uint8_t* comp, size_t comp_bytes, const uint64_t* in_off,
+                           const uint64_t* out_off, size_t n_blocks, uint8_t* out, size_t out_cap, uint8_t* status,
+                           uint64_t* counts);
 
 /* ---- K9: genome-piece sharding of VCF text --------------------------------
  * The reference runs one process per chromosome file (Load/bin/load_vcf_file.py:
