@@ -63,6 +63,11 @@ CADD_ROW_SCORE_HOST, CADD_ROW_BAD = 1, 2
 CADD_NONE, CADD_SNV, CADD_INDEL, CADD_HOST = 0, 1, 2, 255
 CADD_COUNT_ROWS, CADD_COUNT_SCORE_HOST, CADD_COUNT_BAD, CADD_COUNT_ORDER_VIOLATIONS, CADD_N_COUNTS = 0, 1, 2, 3, 4
 CADD_CTR_SNV, CADD_CTR_INDEL, CADD_CTR_NOT_MATCHED, CADD_N_CTRS = 0, 1, 2, 3
+EXIST_FRAG_HOST, EXIST_NONCANON = 1, 2  # AVDB_EXIST_* row flags
+EXIST_ALL_CONTIGS = 0xFFFFFFFF
+EXIST_COUNTS = ("rows", "skipped", "frag_host", "noncanon", "lone_cr", "key_bytes", "pk_bytes",
+                "frag_bytes")  # AVDB_EXIST_COUNT_*, by slot
+EXIST_N_COUNTS = len(EXIST_COUNTS)
 MAX_ALG_ID = 64
 BGZF_STATUS = ("OK", "bad header", "input overrun", "bad block type", "bad stored length", "bad code lengths",
                "bad symbol", "distance before block start", "output longer than ISIZE", "output shorter than ISIZE",
@@ -135,6 +140,8 @@ EXPORTED_SYMBOLS = [
     "avdb_cadd_workspace_size", "avdb_cadd_table_build", "avdb_cadd_match",
     "avdb_cadd_table_build_host", "avdb_cadd_match_host",
     "avdb_bgzf_index_host", "avdb_bgzf_inflate", "avdb_bgzf_inflate_host",
+    "avdb_existing_workspace_size", "avdb_existing_size", "avdb_existing_write",
+    "avdb_existing_size_host", "avdb_existing_write_host",
 ]
 
 
@@ -266,6 +273,11 @@ def _sig(lib):
                                        ctypes.POINTER(ctypes.c_uint64)]
     f.avdb_bgzf_inflate_host.argtypes = [P, P, SZ, P, P, SZ, P, SZ, P, P]
     f.avdb_bgzf_inflate.argtypes = f.avdb_bgzf_inflate_host.argtypes + [P]
+    f.avdb_existing_workspace_size.argtypes = [SZ, SZ, ctypes.POINTER(SZ)]
+    f.avdb_existing_size_host.argtypes = [P, P, SZ, SZ, U32, P, P, P, P, P, P]
+    f.avdb_existing_size.argtypes = f.avdb_existing_size_host.argtypes + [P, SZ, P]
+    f.avdb_existing_write_host.argtypes = [P, P, SZ, SZ, SZ, P, P, P, P, P, P, SZ, P, P, SZ, P, P, SZ, P, P]
+    f.avdb_existing_write.argtypes = f.avdb_existing_write_host.argtypes + [P, SZ, P]
     for name in EXPORTED_SYMBOLS:
         if name not in ("avdb_last_error",):
             getattr(f, name).restype = I32

@@ -95,6 +95,37 @@ class CaddColumns:
                                                                     "end_row")])
 
 
+@dataclass
+class ExistingColumns:
+    """What K12 makes of an export of ``AnnotatedVDB.Variant``
+    (:meth:`Engine.existing_table_build`): the blobs of the metaseq ids, the primary
+    keys and the ``.mapping`` fragments with their ``int64[n_rows + 1]`` offsets, the
+    per-row ``N.EXIST_*`` flags, and the build's counts by name (``N.EXIST_COUNTS``)."""
+    n_rows: int
+    keys: torch.Tensor
+    key_off: torch.Tensor
+    pks: torch.Tensor
+    pk_off: torch.Tensor
+    frag: torch.Tensor
+    frag_off: torch.Tensor
+    flags: torch.Tensor
+    counts: Dict[str, int]
+
+
+def existing_contig_mask(contigs) -> int:
+    """K12's contig mask: ``None`` keeps every row; otherwise one bit per label of
+    ``contigs`` (``CHROM_NAMES`` index; bit 31 for any other label)."""
+    if contigs is None:
+        return N.EXIST_ALL_CONTIGS
+    if isinstance(contigs, int):
+        return contigs & 0xFFFFFFFF
+    mask = 0
+    for c in contigs:
+        c = str(c)
+        mask |= 1 << (CHROM_NAMES.index(c) if c in CHROM_NAMES else 31)
+    return mask
+
+
 _RS_RE = re.compile(r"^rs([1-9][0-9]{0,17})$")
 
 
@@ -1327,6 +1358,97 @@ class Engine:
             key_off.numel() - 1, N.ptr(q) if q.numel() else None, N.ptr(q_off), N.ptr(skip), n, N.ptr(match),
             N.ptr(counters), self._stream()))
         return match[:n]
+
+    # -- K12: the key set's columns from an export --------------------------------
+    def _as_text(self, text) -> torch.Tensor:
+        if isinstance(text, (bytes, bytearray, memoryview)):
+            text = torch.from_numpy(np.frombuffer(bytes(text), dtype=np.uint8).copy()) if len(text) else \
+                torch.zeros(0, dtype=torch.uint8)
+        elif isinstance(text, np.ndarray):
+            text = np.ascontiguousarray(text, dtype=np.uint8)
+            text = torch.from_numpy(text if text.flags.writeable else text.copy())
+        return self._dev(text)
+
+    @staticmethod
+    def _spans(start: torch.Tensor, length: torch.Tensor) -> torch.Tensor:
+        """Flat indices of the spans ``[start[i], start[i] + length[i])``, concatenated."""
+        first = torch.cumsum(length, 0) - length
+        return torch.repeat_interleave(start - first, length) + torch.arange(int(length.sum()), device=start.device)
+
+    def existing_table_build(self, text, contigs=None) -> "ExistingColumns":
+        """K12: a slab of an export of ``AnnotatedVDB.Variant``
+        (``metaseq_id<TAB>record_primary_key<TAB>bin_index[<TAB>...]`` lines; bytes,
+        numpy ``uint8`` or a ``uint8`` tensor) -> :class:`ExistingColumns` on this
+        engine's device, row for row what ``ExistingVariants.from_tsv`` builds.
+        ``contigs``: labels whose rows to keep (``None``: all).  Three syncs: the line
+        count, the size pass's counts (the blobs are allocated from them), the end.
+        Rows whose fragment ``repr`` does not render verbatim (``frag_host``) have
+        their two fields fetched and rendered here, and copied into their spans after
+        the write pass.  On a host-only engine the library's host entries run the same
+        per-line code."""
+        text = self._as_text(text)
+        nb = text.numel()
+        n_lines = self._count_lines(text)
+        m = max(1, n_lines)
+        key_len, pk_len, frag_len = (self.empty(m, torch.int32) for _ in range(3))
+        flags = self.empty(m, torch.uint8)
+        row_off = self.empty(m, torch.int64)
+        counts = self.empty(N.EXIST_N_COUNTS, torch.int64)
+        tp = N.ptr(text) if nb else None
+        tail = []
+        if not self.host_only:
+            sz = ctypes.c_size_t()
+            self.lib.avdb_existing_workspace_size(nb, n_lines, ctypes.byref(sz))
+            ws = self.scratch("existing_build", int(sz.value))
+            tail = [N.ptr(ws), ws.numel(), self._stream()]
+        size = self.lib.avdb_existing_size_host if self.host_only else self.lib.avdb_existing_size
+        N.check("avdb_existing_size", size(self.ctx, tp, nb, n_lines, existing_contig_mask(contigs), N.ptr(key_len),
+                                           N.ptr(pk_len), N.ptr(frag_len), N.ptr(flags), N.ptr(row_off),
+                                           N.ptr(counts), *tail))
+        cnt = dict(zip(N.EXIST_COUNTS, (int(x) for x in counts.cpu().numpy().astype(np.uint64))))
+        if cnt["lone_cr"]:
+            raise ValueError(f"{cnt['lone_cr']} carriage return(s) in the export that no newline follows: Python's "
+                             "text mode ends a line there and the device build does not; load this export with "
+                             "ExistingVariants.from_tsv (--existingHost)")
+        n = cnt["rows"]
+        frag_bytes = cnt["frag_bytes"]
+        host_rows = rendered = None
+        if cnt["frag_host"]:
+            # the rows repr() escapes in: their pk and bin bytes ("pk<TAB>bin") to the host
+            host_rows = torch.nonzero(flags[:n] & N.EXIST_FRAG_HOST).flatten()
+            kl, pl = key_len[host_rows].long(), pk_len[host_rows].long()
+            fl = frag_len[host_rows].long()
+            span = fl - 36 + 1  # len(pk) + 1 + len(bin): the fixed text of a fragment is 36 bytes
+            raw = text[self._spans(row_off[host_rows] + kl + 1, span)].cpu().numpy().tobytes()
+            out, new_len, at = [], [], 0
+            for p, s in zip(pl.tolist(), span.tolist()):
+                pk, bin_ = raw[at:at + p], raw[at + p + 1:at + s]
+                at += s
+                out.append(repr({"primary_key": pk.decode("utf-8"), "bin_index": bin_.decode("utf-8")}).encode("utf-8"))
+                new_len.append(len(out[-1]))
+            new_len = torch.tensor(new_len, dtype=torch.int64)
+            frag_bytes += int(new_len.sum()) - int(fl.sum())
+            frag_len[host_rows] = new_len.to(torch.int32).to(self.device)
+            rendered = (torch.from_numpy(np.frombuffer(b"".join(out), dtype=np.uint8).copy()).to(self.device),
+                        new_len.to(self.device))
+        keys = self.empty(max(1, cnt["key_bytes"]), torch.uint8)
+        pks = self.empty(max(1, cnt["pk_bytes"]), torch.uint8)
+        frag = self.empty(max(1, frag_bytes), torch.uint8)
+        key_off, pk_off, frag_off = (self.empty(n + 1, torch.int64) for _ in range(3))
+        totals = self.empty(4, torch.int64)
+        write = self.lib.avdb_existing_write_host if self.host_only else self.lib.avdb_existing_write
+        N.check("avdb_existing_write", write(self.ctx, tp, nb, n_lines, n, N.ptr(key_len), N.ptr(pk_len),
+                                             N.ptr(frag_len), N.ptr(flags), N.ptr(row_off), N.ptr(keys),
+                                             cnt["key_bytes"], N.ptr(key_off), N.ptr(pks), cnt["pk_bytes"],
+                                             N.ptr(pk_off), N.ptr(frag), frag_bytes, N.ptr(frag_off), N.ptr(totals),
+                                             *tail))
+        if rendered is not None:
+            frag[self._spans(frag_off[host_rows], rendered[1])] = rendered[0]
+        tot = totals.cpu().tolist()
+        if tot[3] or tot[:3] != [cnt["key_bytes"], cnt["pk_bytes"], frag_bytes]:
+            raise N.NativeError("avdb_existing_write", N.AVDB_ERANGE,
+                                f"blob totals {tot[:3]} do not fit the sizes the size pass gave")
+        return ExistingColumns(n, keys, key_off, pks, pk_off, frag, frag_off, flags[:n], cnt)
 
     # -- K10: CADD table and allele join ---------------------------------------
     def new_cadd_counters(self) -> torch.Tensor:

@@ -26,10 +26,19 @@ keys K7 rendered (``avdb_keyset_probe_text``).  A primary key without an externa
 id equals the metaseq id, which the ``--skipExisting`` check already looked up,
 so a key set over the exported primary keys answers the same as a
 ``map_variants`` lookup would on a consistent export (unpinned, as above).
+
+The key set is made from the export either row by row on the host
+(:meth:`ExistingVariants.from_tsv`, the constructor) or, for exports of the
+table's real size, on the device (:meth:`ExistingVariants.from_export`, K12
+``avdb_existing_size`` / ``avdb_existing_write``): the same blobs and tables,
+with no Python object per row.
 """
 
 from __future__ import annotations
 
+import ast
+import gzip
+import os
 from typing import Dict, Iterable, List, Optional, Sequence, Tuple
 
 import numpy as np
@@ -47,6 +56,7 @@ class ExistingVariants(object):
         self._pks: List[str] = list(primary_keys) if primary_keys is not None else []
         self._pk_set = None
         self._pk_dev = None
+        self._cols = None
         ids: List[str] = []
         self._payload: List[List[dict]] = []
         for metaseq, match in entries:
@@ -73,7 +83,7 @@ class ExistingVariants(object):
         self.frag_off = torch.from_numpy(foff).to(dev)
 
     def __len__(self):
-        return len(self._ids)
+        return len(self._ids) if self._cols is None else self._cols.n_rows
 
     @classmethod
     def from_tsv(cls, path: str, **kw) -> "ExistingVariants":
@@ -90,7 +100,52 @@ class ExistingVariants(object):
                 pks.append(f[1])
         return cls(entries, primary_keys=pks, **kw)
 
+    @classmethod
+    def from_export(cls, path_or_text, contigs: Optional[Sequence[str]] = None, engine=None,
+                    check_alt: bool = True) -> "ExistingVariants":
+        """The same key set as :meth:`from_tsv`, built on the device (K12,
+        ``Engine.existing_table_build``) with no per-row Python object: the export as
+        a path (plain, bgzip — inflated on the device, the text never visits the
+        host — or single-member gzip) or as its text (bytes, numpy or a ``uint8``
+        tensor).  ``contigs``: keep only the rows of these contig labels
+        (``chromosomes.CHROM_NAMES``; any other label stands for all the others).
+        What a row means to the host (:meth:`payload`, :meth:`resolve_host`) and the
+        primary-key table are made on first use."""
+        from .engine import default_engine
+        eng = engine or default_engine()
+        text = path_or_text
+        if isinstance(text, (str, os.PathLike)):
+            text = cls._read_export(os.fspath(text), eng)
+        self = cls.__new__(cls)
+        self._engine = eng
+        self.check_alt = check_alt
+        self._pk_set = self._pk_dev = self._index = None
+        self._cols = c = eng.existing_table_build(text, contigs)
+        self.keys, self.key_off = c.keys, c.key_off
+        self.frag, self.frag_off = c.frag, c.frag_off
+        self.table = eng.keyset_build(c.keys, c.key_off)
+        return self
+
+    @staticmethod
+    def _read_export(path: str, eng):
+        from . import bgzf
+        if bgzf.is_bgzf(path):
+            try:
+                return bgzf.BgzfFile(path, eng).read()
+            except bgzf.NotBgzf:
+                pass
+        with open(path, "rb") as fh:
+            magic = fh.read(2)
+        with (gzip.open if magic == b"\x1f\x8b" else open)(path, "rb") as fh:
+            return fh.read()
+
+    def _row_bytes(self, blob: torch.Tensor, off: torch.Tensor, k: int) -> bytes:
+        a, b = off[k:k + 2].tolist()
+        return blob[a:b].cpu().numpy().tobytes()
+
     def payload(self, k: int) -> List[dict]:
+        if self._cols is not None:  # the fragment is the repr of the row's one-entry list
+            return [ast.literal_eval(self._row_bytes(self.frag, self.frag_off, k).decode("utf-8"))]
         return self._payload[k]
 
     def probe(self, batch, counters=None):
@@ -102,8 +157,21 @@ class ExistingVariants(object):
         same lookup on the host over the exported ids."""
         if self._index is None:
             self._index = {}
-            for i, x in enumerate(self._ids):
-                self._index.setdefault(x, i)
+            if self._cols is not None:
+                # a record of kind AVDB_MATCH_HOST has a non-canonical label, which the
+                # switched form keeps: only rows with such a label can equal it
+                from . import _native as N
+                c = self._cols
+                rows = torch.nonzero(c.flags & N.EXIST_NONCANON).flatten()
+                a, b = c.key_off[rows], c.key_off[rows + 1]
+                blob = c.keys[self._engine._spans(a, b - a)].cpu().numpy().tobytes() if rows.numel() else b""
+                at = 0
+                for i, n in zip(rows.tolist(), (b - a).tolist()):
+                    self._index.setdefault(blob[at:at + n].decode("utf-8"), i)
+                    at += n
+            else:
+                for i, x in enumerate(self._ids):
+                    self._index.setdefault(x, i)
         k = self._index.get(metaseq, -1)
         if k < 0 and self.check_alt:
             c, p, r, a = metaseq.split(":")
@@ -115,11 +183,32 @@ class ExistingVariants(object):
 
     # ---- primary keys (ADSP is_duplicate(recordPK)) ---------------------------
     def has_primary_key(self, pk: str) -> bool:
+        if self._cols is not None:
+            return self.has_primary_keys([pk])[0]
         if self._pk_set is None:
             self._pk_set = set(self._pks)
         return pk in self._pk_set
 
+    def has_primary_keys(self, pks: Sequence[Optional[str]]) -> List[bool]:
+        """``has_primary_key`` of each entry (``None``: ``False``); on a device-built
+        set one K6 launch over all of them."""
+        if self._cols is None:
+            return [pk is not None and self.has_primary_key(pk) for pk in pks]
+        if not len(pks):
+            return []
+        kb = [b"" if pk is None else pk.encode("utf-8") for pk in pks]
+        off = np.zeros(len(kb) + 1, dtype=np.int64)
+        np.cumsum(np.fromiter((len(x) for x in kb), dtype=np.int64, count=len(kb)), out=off[1:])
+        dev = self._engine.device
+        text = torch.from_numpy(np.frombuffer(b"".join(kb) or b"\0", dtype=np.uint8).copy()).to(dev)
+        skip = torch.tensor([pk is None for pk in pks], dtype=torch.uint8).to(dev)
+        m = self.probe_primary_keys(text, torch.from_numpy(off).to(dev), len(kb), skip=skip)
+        return (m >= 0).cpu().tolist()
+
     def _pk_table(self):
+        if self._pk_dev is None and self._cols is not None:
+            c = self._cols
+            self._pk_dev = (c.pks, c.pk_off, self._engine.keyset_build(c.pks, c.pk_off))
         if self._pk_dev is None:
             kb = [x.encode("utf-8") for x in self._pks]
             off = np.zeros(len(kb) + 1, dtype=np.int64)

@@ -56,7 +56,12 @@ def parse_args(argv: Optional[Sequence[str]] = None):
     ap.add_argument("-m", "--chromosomeMap", help="tab-delimited source_id -> chromosome map (e.g. RefSeq "
                     "accessions used as CHROM), parsers.ChromosomeMap")
     ap.add_argument("--skipExisting", action="store_true")
-    ap.add_argument("--existing", help="export of AnnotatedVDB.Variant: metaseq_id<TAB>record_primary_key<TAB>bin_index")
+    ap.add_argument("--existing", help="export of AnnotatedVDB.Variant: metaseq_id<TAB>record_primary_key<TAB>bin_index "
+                                       "lines; a plain, gzip or bgzip file, made into the key set on the GPU")
+    ap.add_argument("--existingContigs", help="comma-separated contig labels (1..22, X, Y, M; any other label stands "
+                                              "for all the others): keep only their rows of --existing (default: all)")
+    ap.add_argument("--existingHost", action="store_true",
+                    help="read --existing (a plain file) row by row on the host instead")
     ap.add_argument("--algInvocationId", default="0", help="row_algorithm_id of the COPY rows")
     ap.add_argument("--dedup", action="store_true", help="drop in-batch duplicate primary keys (keep first)")
     ap.add_argument("--batchBytes", type=int, default=256 << 20)
@@ -163,7 +168,13 @@ def make_loader(args, device: int):
         ld.set_chromosome_map(ChromosomeMap(args.chromosomeMap))
     if args.skipExisting:
         from .existing import ExistingVariants
-        ld.set_skip_existing(True, existing=ExistingVariants.from_tsv(args.existing, engine=ld._engine))
+        if getattr(args, "existingHost", False):
+            existing = ExistingVariants.from_tsv(args.existing, engine=ld._engine)
+        else:
+            labels = getattr(args, "existingContigs", None)
+            contigs = [c for c in labels.split(",") if c] if labels else None
+            existing = ExistingVariants.from_export(args.existing, contigs=contigs, engine=ld._engine)
+        ld.set_skip_existing(True, existing=existing)
     return ld
 
 

@@ -1140,7 +1140,7 @@ class VCFVariantLoader(object):
         self._match = None
         self._adsp_dup = None
         if self.is_adsp() and self._existing is not None:
-            self._adsp_dup = [pk is not None and self._existing.has_primary_key(pk) for pk in pks]
+            self._adsp_dup = self._existing.has_primary_keys(pks)
         disp = [d if st == 0 else None for d, st in zip(res["display"], res["disp_state"])]
         return res["path"], pks, None, disp
 
@@ -1188,7 +1188,7 @@ class VCFVariantLoader(object):
         # ADSP: is_duplicate(recordPK) against the exported keys (vcf_variant_loader.py:303-307)
         self._adsp_dup = None
         if self.is_adsp() and self._existing is not None:
-            self._adsp_dup = [pk is not None and self._existing.has_primary_key(pk) for pk in pks]
+            self._adsp_dup = self._existing.has_primary_keys(pks)
         return paths, pks, keep, disp
 
     def _emit(self, parsed, recs, paths, pks, keep, disp, errors):

@@ -848,6 +848,77 @@ int avdb_bgzf_inflate_host(const avdb_ctx* ctx, const uint8_t* comp, size_t comp
                            const uint64_t* out_off, size_t n_blocks, uint8_t* out, size_t out_cap, uint8_t* status,
                            uint64_t* counts);
 
+/* ---- K12: the --skipExisting key set from an export ------------------------------
+ * Replaces the per-row host loop that turns an export of AnnotatedVDB.Variant,
+ * `metaseq_id<TAB>record_primary_key<TAB>bin_index[<TAB>...]` lines separated by '\n',
+ * into what K6 and K5 take: the key blob avdb_keyset_build hashes, the primary-key
+ * blob avdb_keyset_probe_text's table is built over, and avdb_format_opts.frag /
+ * frag_off.  `text` is a slab of the export; n_lines its line count (newlines, plus one
+ * when the text does not end in one), as for K0 and K10a.
+ * Row rule: one trailing '\r' before the '\n' is stripped; a line with fewer than 3
+ * tab-separated fields, or whose first field is exactly `metaseq_id`, is skipped;
+ * every other line is a row, in file order; fields after the third are ignored and
+ * empty fields allowed.  A '\r' no '\n' follows is not a line end here (it is one for
+ * Python's text mode): such bytes are counted in counts[AVDB_EXIST_COUNT_LONE_CR] and
+ * the caller decides.  contig_mask: bit c for the canonical contig label c (1..22, X,
+ * Y, M), bit 31 for every other label; the label is the text before the first ':' of
+ * the metaseq id; a row whose bit is clear is skipped as if its line were absent
+ * (AVDB_EXIST_ALL_CONTIGS keeps everything).
+ *   1. avdb_existing_size : per row (n_lines entries allocated, rows written)
+ *      key_len, pk_len, frag_len, flags and row_off (u64: the offset of the row's line
+ *      in the slab; its pk field starts key_len + 1 bytes on), and counts (8 x u64,
+ *      set by the call).
+ *      frag_len is the length of {'primary_key': '<pk>', 'bin_index': '<bin>'}, the
+ *      repr of the row's one-entry match list.  AVDB_EXIST_FRAG_HOST: the pk or bin
+ *      field holds a byte outside 0x20..0x7E, a ' or a \, which repr does not render
+ *      verbatim: the caller renders that fragment, and stores its length in
+ *      frag_len[row] before the write pass.  AVDB_EXIST_NONCANON: the contig label is
+ *      not one of the 25.
+ *   2. avdb_existing_write (n_rows = counts[AVDB_EXIST_COUNT_ROWS]; the same text and
+ *      n_lines, and the arrays the size pass wrote):
+ *      scans the three length arrays into key_off / pk_off / frag_off (n_rows + 1
+ *      entries each) and writes the blobs (8-byte aligned, caps in bytes).  The
+ *      fragment span of a FRAG_HOST row is left unwritten.  totals (4 x u64): the three
+ *      blob sizes and the number of blobs larger than their cap.  Nothing outside
+ *      [0, total) of a blob is written, and nothing at all when a cap is too small:
+ *      the host entry returns AVDB_ERANGE then; the device entry, which does not wait
+ *      for its own scan, returns AVDB_OK and leaves totals[3] != 0 for the caller to
+ *      read after the stream.  Lengths or row offsets that do not
+ *      describe the text read as zero bytes, never outside the slab.
+ * Workspace: avdb_existing_workspace_size bytes, 256-byte aligned; the device entries
+ * allocate nothing per call.  The _host entries run the same per-line code on host
+ * pointers, on an avdb_ctx_create(-1, ...) context. */
+#define AVDB_EXIST_FRAG_HOST 0x01u
+#define AVDB_EXIST_NONCANON 0x02u
+#define AVDB_EXIST_ALL_CONTIGS 0xFFFFFFFFu
+#define AVDB_EXIST_COUNT_ROWS 0
+#define AVDB_EXIST_COUNT_SKIPPED 1      /* lines that are no row */
+#define AVDB_EXIST_COUNT_FRAG_HOST 2
+#define AVDB_EXIST_COUNT_NONCANON 3
+#define AVDB_EXIST_COUNT_LONE_CR 4
+#define AVDB_EXIST_COUNT_KEY_BYTES 5    /* blob totals with the size pass's own frag_len */
+#define AVDB_EXIST_COUNT_PK_BYTES 6
+#define AVDB_EXIST_COUNT_FRAG_BYTES 7
+#define AVDB_EXIST_N_COUNTS 8
+int avdb_existing_workspace_size(size_t text_bytes, size_t n_lines, size_t* bytes);
+int avdb_existing_size(avdb_ctx* ctx, const uint8_t* text, size_t text_bytes, size_t n_lines, uint32_t contig_mask,
+                       uint32_t* key_len, uint32_t* pk_len, uint32_t* frag_len, uint8_t* flags, uint64_t* row_off, uint64_t* counts,
+                       void* workspace, size_t workspace_bytes, void* stream);
+int avdb_existing_write(avdb_ctx* ctx, const uint8_t* text, size_t text_bytes, size_t n_lines, size_t n_rows,
+                        const uint32_t* key_len, const uint32_t* pk_len, const uint32_t* frag_len,
+                        const uint8_t* flags, const uint64_t* row_off, uint8_t* keys, size_t keys_cap,
+                        uint64_t* key_off, uint8_t* pks, size_t pks_cap, uint64_t* pk_off, uint8_t* frag,
+                        size_t frag_cap, uint64_t* frag_off, uint64_t* totals, void* workspace,
+                        size_t workspace_bytes, void* stream);
+int avdb_existing_size_host(const avdb_ctx* ctx, const uint8_t* text, size_t text_bytes, size_t n_lines,
+                            uint32_t contig_mask, uint32_t* key_len, uint32_t* pk_len, uint32_t* frag_len,
+                            uint8_t* flags, uint64_t* row_off, uint64_t* counts);
+int avdb_existing_write_host(const avdb_ctx* ctx, const uint8_t* text, size_t text_bytes, size_t n_lines,
+                             size_t n_rows, const uint32_t* key_len, const uint32_t* pk_len,
+                             const uint32_t* frag_len, const uint8_t* flags, const uint64_t* row_off, uint8_t* keys,
+                             size_t keys_cap, uint64_t* key_off, uint8_t* pks, size_t pks_cap, uint64_t* pk_off,
+                             uint8_t* frag, size_t frag_cap, uint64_t* frag_off, uint64_t* totals);
+
 /* ---- K9: genome-piece sharding of VCF text --------------------------------
  * The reference runs one process per chromosome file (Load/bin/load_vcf_file.py:
  * 307-313).  One file is split over the ranks of a node by a piece plan
