@@ -13,6 +13,7 @@ indexes and virtual offsets are not read; BGZF is not written.
 
 from __future__ import annotations
 
+import gzip
 from dataclasses import dataclass
 from typing import Iterator, Optional
 
@@ -64,6 +65,25 @@ def is_bgzf(path: str) -> bool:
         h = fh.read(18)
     return len(h) == 18 and h[:4] == b"\x1f\x8b\x08\x04" and h[12:16] == b"BC\x02\x00" and \
         int.from_bytes(h[10:12], "little") >= 6
+
+
+def open_text(path: str):
+    """``path`` opened for reading bytes: through ``gzip`` when it starts with the gzip magic, else as it is."""
+    with open(path, "rb") as fh:
+        magic = fh.read(2)
+    return (gzip.open if magic == b"\x1f\x8b" else open)(path, "rb")
+
+
+def read_whole(path: str, engine):
+    """A plain, gzip or bgzip file's text: a ``uint8`` tensor on ``engine``'s device for
+    bgzip (K11 inflates it there, the text never visits the host), else ``bytes``."""
+    if is_bgzf(path):
+        try:
+            return BgzfFile(path, engine).read()
+        except NotBgzf:
+            pass
+    with open_text(path) as fh:
+        return fh.read()
 
 
 def _last_newline(t: torch.Tensor) -> int:

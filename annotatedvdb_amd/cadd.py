@@ -12,7 +12,7 @@ at the position, in file order, with ``ref in [R, A] and alt in [R, A]``
 (``:202-204`` — deliberately that loose: a switched row matches).
 
 A bgzip file read whole (``CaddTable.from_file(path)``) is inflated on the GPU (K11,
-``bgzf.BgzfFile``) and the text handed to the table build where it lies: no host
+``bgzf.read_whole``) and the text handed to the table build where it lies: no host
 copy of the text exists.  Tabix indexes are not read.  A whole-genome SNV file does
 not fit in HBM: ``CaddTable.from_file(path, contigs=[...])`` keeps one chromosome's
 lines while it reads, the way the reference's loop runs per chromosome; that filter
@@ -29,7 +29,6 @@ of a variant's primary key by metaseq id (``__get_variant_primary_key`` →
 
 from __future__ import annotations
 
-import gzip
 import json
 from typing import Dict, Iterable, List, Optional, Sequence
 
@@ -87,25 +86,17 @@ class CaddTable(object):
         these contigs (CADD labels: ``'1'`` .. ``'22'``, ``'X'``, ``'Y'``, ``'MT'``; ``'M'``
         and a ``chr`` prefix are accepted) while reading."""
         from . import bgzf
-        if contigs is None and bgzf.is_bgzf(path):
+        if contigs is None:
             from .engine import default_engine
             engine = engine or default_engine()
-            try:
-                return cls(engine.cadd_table_build(bgzf.BgzfFile(path, engine).read()), engine)
-            except bgzf.NotBgzf:
-                pass
-        with open(path, "rb") as fh:
-            magic = fh.read(2)
-        opener = gzip.open if magic == b"\x1f\x8b" else open
-        with opener(path, "rb") as fh:
-            if contigs is None:
-                return cls.from_text(fh.read(), engine)
-            keep = set()
-            for c in contigs:
-                c = str(c)
-                c = c[3:] if c.startswith("chr") else c
-                keep.add(_cadd_name(c).encode() + b"\t")
-            keep = tuple(keep)
+            return cls.from_text(bgzf.read_whole(path, engine), engine)
+        keep = set()
+        for c in contigs:
+            c = str(c)
+            c = c[3:] if c.startswith("chr") else c
+            keep.add(_cadd_name(c).encode() + b"\t")
+        keep = tuple(keep)
+        with bgzf.open_text(path) as fh:
             return cls.from_text(b"".join(ln for ln in fh if ln.startswith(keep)), engine)
 
     # ---- host-side pieces ---------------------------------------------------

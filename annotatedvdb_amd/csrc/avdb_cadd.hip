@@ -4,13 +4,11 @@
 // allele membership test (Util/lib/python/loaders/cadd_updater.py:175-221, driven
 // by Load/bin/load_cadd_scores.py) with a table built once from the CADD text and
 // a sort-merge join of each record batch against it:
-//   (K0's count and line-starts passes, avdb::text_line_starts: one start per line)
-//   k_cadd_mark    one lane per line: 1 for a data line (not empty, not '#'); the
-//                  exclusive scan of the marks (avdb_scan.hpp) numbers the rows
-//   k_cadd_parse   one lane per line (256 lines' text staged in LDS): tab fields,
-//                  contig code, POS, allele spans
-//                  (offsets into the slab, nothing copied), the two scores as
-//                  correctly rounded doubles (avdb_cadd.hpp parse_score)
+//   (avdb_lines.hpp, shared with K12: one start per line, the marks scanned into row numbers)
+//   k_cadd_mark    one lane per line: 1 for a data line (not empty, not '#')
+//   k_cadd_parse   one lane per line (lines::for_each_line: 256 lines' text staged in
+//                  LDS): tab fields, contig code, POS, allele spans (offsets into the slab,
+//                  nothing copied), the two scores as correctly rounded doubles (parse_score)
 //   k_cadd_index   one lane per row: run starts / ends per contig -> first_row /
 //                  end_row, and the order violations tabix would refuse
 //   k_cadd_match   one lane per record: table by allele lengths, lower_bound of pos
@@ -19,9 +17,6 @@
 //                  lanes to neighbouring rows
 // The per-line and per-record code is avdb_cadd.hpp, shared with the _host entries.
 #include "avdb_cadd.hpp"
-
-#include "avdb_scan.hpp"
-#include "avdb_text.hpp"
 
 #include <string.h>
 
@@ -39,56 +34,32 @@ __global__ __launch_bounds__(kBlock) void k_cadd_mark(const uint8_t* __restrict_
     uint64_t m = 0;
     if (li < n_lines) {
       uint64_t s, e;
-      cadd::line_span(text, text_bytes, starts, n_lines, li, &s, &e);
+      lines::line_span(text, text_bytes, starts, n_lines, li, &s, &e);
       m = cadd::is_data_line(text, s, e);
     }
     mark[li] = m;  // mark[n_lines] = 0: the scan leaves the row count there
   }
 }
 
-__device__ __forceinline__ void wave_add(unsigned long long* dst, uint32_t v) {
-  for (int d = 32; d > 0; d >>= 1) v += __shfl_down(v, d, kWave);
-  if (__lane_id() == 0 && v) atomicAdd(dst, (unsigned long long)v);
-}
-
 __global__ __launch_bounds__(kBlock) void k_cadd_parse(const uint8_t* __restrict__ text, size_t text_bytes,
                                                        const uint64_t* __restrict__ starts, size_t n_lines,
                                                        const uint64_t* __restrict__ row_of, Cols o,
                                                        unsigned long long* __restrict__ counts) {
-  // 256 consecutive lines per trip, their text staged in LDS with coalesced 16-byte
-  // loads (as k_vcf_parse): a lane's byte-by-byte walk of its line then waits on LDS,
-  // not on one global round trip per byte (reading global bytes this kernel took
-  // 12.6 ms of a 17.3 ms build of 104 M lines; staged, the build takes 9.4 ms).  A
-  // span over kCaddStage bytes is parsed from global memory.
+  // (reading global bytes this kernel took 12.6 ms of a 17.3 ms build of 104 M lines; staged, the build takes 9.4 ms)
   __shared__ u32x4 s_text[kCaddStage / 16];
-  const Heap h = make_heap(text, text_bytes);
   uint32_t n_host = 0, n_bad = 0;
-  for (size_t base = size_t(blockIdx.x) * kBlock; base < n_lines; base += size_t(gridDim.x) * kBlock) {
-    const size_t last = base + kBlock < n_lines ? base + kBlock : n_lines;
-    uint64_t s0 = starts[base], s1 = last < n_lines ? starts[last] : text_bytes;
-    if (s0 > text_bytes) s0 = text_bytes;
-    if (s1 > text_bytes || s1 < s0) s1 = text_bytes;
-    const Window w = stage_window<kBlock, kCaddStage>(h, s0, s1, s_text);
-    const size_t li = base + threadIdx.x;
-    if (li < n_lines) {
-      const uint64_t r = row_of[li];
-      if (row_of[li + 1] != r) {  // a data line
-        uint64_t s, e;
-        cadd::line_span(text, text_bytes, starts, n_lines, li, &s, &e);
-        uint32_t f;
-        if (w.staged && s >= s0 && e <= s1)
-          f = cadd::parse_row((lds_cp)(reinterpret_cast<const uint8_t*>(s_text) + (h.lo + s - w.a0)), s, e - s, r, o);
-        else
-          f = cadd::parse_row((glb_cp)(text + s), s, e - s, r, o);
-        n_host += (f & AVDB_CADD_ROW_SCORE_HOST) != 0;
-        n_bad += (f & AVDB_CADD_ROW_BAD) != 0;
-      }
-    }
-    __syncthreads();  // the stage is reused by the next trip
-  }
+  lines::for_each_line<kCaddStage>(text, text_bytes, starts, n_lines, s_text, [&](size_t li, auto with_line) {
+    const uint64_t r = row_of[li];
+    if (row_of[li + 1] == r) return;  // not a data line
+    with_line([&](uint64_t s, uint64_t len, bool, auto line) {
+      const uint32_t f = cadd::parse_row(line, s, len, r, o);
+      n_host += (f & AVDB_CADD_ROW_SCORE_HOST) != 0;
+      n_bad += (f & AVDB_CADD_ROW_BAD) != 0;
+    });
+  });
   if (blockIdx.x == 0 && threadIdx.x == 0) counts[AVDB_CADD_COUNT_ROWS] = row_of[n_lines];
-  wave_add(&counts[AVDB_CADD_COUNT_SCORE_HOST], n_host);
-  wave_add(&counts[AVDB_CADD_COUNT_BAD], n_bad);
+  lines::wave_add(&counts[AVDB_CADD_COUNT_SCORE_HOST], n_host);
+  lines::wave_add(&counts[AVDB_CADD_COUNT_BAD], n_bad);
 }
 
 // runs: u32[kContigs] run starts seen per contig (zeroed by the caller)
@@ -112,7 +83,7 @@ __global__ __launch_bounds__(kBlock) void k_cadd_index(const uint8_t* __restrict
       if (ev.end) atomicMax(&end_row[ev.contig], uint32_t(i + 1));
     }
   }
-  wave_add(&counts[AVDB_CADD_COUNT_ORDER_VIOLATIONS], viol);
+  lines::wave_add(&counts[AVDB_CADD_COUNT_ORDER_VIOLATIONS], viol);
 }
 
 __global__ __launch_bounds__(kBlock) void k_cadd_match(View snv, View indel, const uint8_t* __restrict__ chrom,
@@ -139,9 +110,9 @@ __global__ __launch_bounds__(kBlock) void k_cadd_match(View snv, View indel, con
     n_none += k == AVDB_CADD_NONE;
   }
   if (ctr) {
-    wave_add(&ctr[AVDB_CADD_CTR_SNV], n_snv);
-    wave_add(&ctr[AVDB_CADD_CTR_INDEL], n_indel);
-    wave_add(&ctr[AVDB_CADD_CTR_NOT_MATCHED], n_none);
+    lines::wave_add(&ctr[AVDB_CADD_CTR_SNV], n_snv);
+    lines::wave_add(&ctr[AVDB_CADD_CTR_INDEL], n_indel);
+    lines::wave_add(&ctr[AVDB_CADD_CTR_NOT_MATCHED], n_none);
   }
 }
 
@@ -149,18 +120,14 @@ __global__ __launch_bounds__(kBlock) void k_cadd_match(View snv, View indel, con
 
 using namespace avdb;
 
-static size_t pad256(size_t x) { return (x + 255) & ~size_t(255); }
-
-// workspace: count workspace | line starts | marks / row numbers | scan temp | runs
-struct CaddLayout {
-  size_t starts, row_of, scan, scan_bytes, runs, total;
+// workspace: lines::Layout | scan temp | runs
+struct CaddLayout : lines::Layout {
+  size_t runs, total;
 };
 static CaddLayout cadd_layout(size_t n_lines) {
-  CaddLayout L;
-  L.starts = AVDB_VCF_COUNT_WORKSPACE_BYTES;
-  L.row_of = L.starts + pad256(8 * n_lines);
-  L.scan = L.row_of + pad256(8 * (n_lines + 1));
-  L.scan_bytes = pad256(scan::workspace_bytes(n_lines + 1));
+  CaddLayout L{lines::layout(n_lines)};
+  L.scan = L.next;
+  L.scan_bytes = lines::pad256(scan::workspace_bytes(n_lines + 1));
   L.runs = L.scan + L.scan_bytes;
   L.total = L.runs + 256;
   return L;
@@ -177,9 +144,7 @@ static const char* build_args_error(const void* ctx, const uint8_t* text, size_t
                                     const Cols& o, const uint32_t* first_row, const uint32_t* end_row,
                                     const uint64_t* counts) {
   if (!ctx || !first_row || !end_row || !counts) return "null argument";
-  if (text_bytes && !text) return "null text";
-  if (n_lines >= 0x7FFFFFFFull) return "too many lines (rows are numbered in int32)";
-  if (n_lines > text_bytes) return "more lines than text bytes";
+  if (const char* err = lines::text_args_error(text, text_bytes, n_lines)) return err;
   if (n_lines && (!o.chrom || !o.pos || !o.ref_off || !o.ref_len || !o.alt_off || !o.alt_len || !o.raw || !o.phred ||
                   !o.flags))
     return "null column";
@@ -197,10 +162,8 @@ extern "C" int avdb_cadd_table_build(avdb_ctx* ctx, const uint8_t* text, size_t 
     return AVDB_EINVAL;
   }
   const CaddLayout L = cadd_layout(n_lines);
-  if (n_lines && (!workspace || workspace_bytes < L.total || reinterpret_cast<uintptr_t>(workspace) % 256)) {
-    avdb_set_error("avdb_cadd_table_build: 256-byte aligned workspace of %zu bytes required", L.total);
-    return AVDB_ERANGE;
-  }
+  if (n_lines)
+    if (int e = lines::workspace_error("avdb_cadd_table_build", L.total, workspace, workspace_bytes)) return e;
   AVDB_HIP_TRY(hipSetDevice(ctx->device));
   hipStream_t s = static_cast<hipStream_t>(stream);
   AVDB_HIP_TRY(hipMemsetAsync(counts, 0, 8 * AVDB_CADD_N_COUNTS, s));
@@ -208,19 +171,16 @@ extern "C" int avdb_cadd_table_build(avdb_ctx* ctx, const uint8_t* text, size_t 
   AVDB_HIP_TRY(hipMemsetAsync(end_row, 0, 4 * AVDB_CADD_N_CONTIGS, s));
   if (n_lines == 0) return AVDB_OK;
   char* w = static_cast<char*>(workspace);
-  auto* starts = reinterpret_cast<uint64_t*>(w + L.starts);
-  auto* row_of = reinterpret_cast<uint64_t*>(w + L.row_of);
+  auto* starts = reinterpret_cast<const uint64_t*>(w + L.starts);
+  auto* row_of = reinterpret_cast<const uint64_t*>(w + L.row_of);
   auto* runs = reinterpret_cast<uint32_t*>(w + L.runs);
   auto* cnt = reinterpret_cast<unsigned long long*>(counts);
   AVDB_HIP_TRY(hipMemsetAsync(runs, 0, 256, s));
-  // a start the starts pass does not write (n_lines above the text's own count)
-  // stays past the text: line_span reads such a line as empty
-  AVDB_HIP_TRY(hipMemsetAsync(starts, 0xFF, 8 * n_lines, s));
-  if (int e = text_line_starts(text, text_bytes, n_lines, w, starts, s)) return e;
   const unsigned grid = stream_grid(n_lines + 1, kBlock, 4096);
-  hipLaunchKernelGGL(k_cadd_mark, dim3(grid), dim3(kBlock), 0, s, text, text_bytes, starts, n_lines, row_of);
-  AVDB_LAUNCH_CHECK("k_cadd_mark");
-  if (int e = scan::exclusive_u64(row_of, row_of, n_lines + 1, w + L.scan, L.scan_bytes, s)) return e;
+  auto mark = [&](const uint64_t* st, uint64_t* marks) {
+    hipLaunchKernelGGL(k_cadd_mark, dim3(grid), dim3(kBlock), 0, s, text, text_bytes, st, n_lines, marks);
+  };
+  if (int e = lines::number_rows(text, text_bytes, n_lines, w, L, s, "k_cadd_mark", mark)) return e;
   hipLaunchKernelGGL(k_cadd_parse, dim3(grid), dim3(kBlock), 0, s, text, text_bytes, starts, n_lines, row_of, o, cnt);
   AVDB_LAUNCH_CHECK("k_cadd_parse");
   hipLaunchKernelGGL(k_cadd_index, dim3(grid), dim3(kBlock), 0, s, chrom, pos, flags, row_of + n_lines, n_lines,
@@ -293,16 +253,11 @@ extern "C" int avdb_cadd_table_build_host(const avdb_ctx* ctx, const uint8_t* te
   memset(first_row, 0xFF, 4 * AVDB_CADD_N_CONTIGS);
   memset(end_row, 0, 4 * AVDB_CADD_N_CONTIGS);
   if (n_lines == 0) return AVDB_OK;
-  // line 0 starts at 0, line k + 1 after the k-th newline (as k_vcf_starts)
-  std::vector<uint64_t> starts(n_lines, ~0ull);
-  starts[0] = 0;
-  size_t k = 1;
-  for (size_t i = 0; i < text_bytes && k < n_lines; ++i)
-    if (text[i] == '\n') starts[k++] = i + 1;
+  const std::vector<uint64_t> starts = lines::host_line_starts(text, text_bytes, n_lines);
   uint64_t rows = 0;
   for (size_t li = 0; li < n_lines; ++li) {
     uint64_t s, e;
-    cadd::line_span(text, text_bytes, starts.data(), n_lines, li, &s, &e);
+    lines::line_span(text, text_bytes, starts.data(), n_lines, li, &s, &e);
     if (!cadd::is_data_line(text, s, e)) continue;
     const uint32_t f = cadd::parse_row(text + s, s, e - s, rows++, o);
     counts[AVDB_CADD_COUNT_SCORE_HOST] += (f & AVDB_CADD_ROW_SCORE_HOST) != 0;

@@ -1,10 +1,10 @@
 // K10 — per-line and per-record arithmetic of the CADD table build and the allele
 // join, shared by the kernels (avdb_cadd.hip) and the library's host entries
 // (avdb_cadd_table_build_host / avdb_cadd_match_host): one definition, compiled
-// for both sides, as avdb_vcfline.hpp and avdb_k5.hpp are.
+// for both sides, as avdb_vcfline.hpp and avdb_k5.hpp are (line spans: avdb_lines.hpp).
 #pragma once
 
-#include "avdb_internal.hpp"
+#include "avdb_lines.hpp"
 
 namespace avdb {
 namespace cadd {
@@ -100,22 +100,6 @@ AVDB_HD uint32_t contig_code(CP p, uint32_t n) {
     }
   }
   return kUnknown;
-}
-
-// line li of the text is bytes [*s, *e) (its '\n' excluded).  starts[] comes from
-// the line-starts pass; a start the caller's n_lines does not bear out gives an
-// empty span, so nothing is read outside the text.
-AVDB_HD void line_span(const uint8_t* text, uint64_t text_bytes, const uint64_t* starts, uint64_t n_lines, uint64_t li,
-                       uint64_t* s, uint64_t* e) {
-  uint64_t a = starts[li];
-  const bool last = li + 1 >= n_lines || starts[li + 1] > text_bytes;
-  uint64_t b = last ? text_bytes : starts[li + 1] - 1;
-  if (a > text_bytes) a = text_bytes;
-  if (b > text_bytes) b = text_bytes;
-  if (b < a) b = a;
-  if (last && b > a && text[b - 1] == '\n') --b;  // the last line's own newline
-  *s = a;
-  *e = b;
 }
 
 // a data line: not empty and not a '#' header line

@@ -5,11 +5,10 @@
 // (a split, a one-entry list of a dict, two encodes, a repr and three joins per
 // exported row) with two passes over the export text on the device:
 //   size pass (avdb_existing_size)
-//     (K0's line-starts pass, avdb::text_line_starts: one start per line)
-//     k_exist_lines    one lane per line (256 lines' text staged in LDS): from_tsv's
-//                      row rule, the three field lengths, the row's flags, the lone
-//                      '\r' count; 16 bytes of line info and a row mark per line
-//     (exclusive scan of the marks, avdb_scan.hpp: the rows numbered in file order)
+//     (avdb_lines.hpp, shared with K10: one start per line, the marks scanned into row numbers)
+//     k_exist_lines    one lane per line (lines::for_each_line: 256 lines' text staged
+//                      in LDS): from_tsv's row rule, the three field lengths, the row's
+//                      flags, the lone '\r' count; 16 bytes of info and a mark per line
 //     k_exist_compact  one lane per line: a row's lengths, flags and line start to
 //                      its row number; the counts
 //   write pass (avdb_existing_write)
@@ -20,9 +19,6 @@
 //                      one word per lane (see below)
 // The per-line and per-row code is avdb_existing.hpp, shared with the _host entries.
 #include "avdb_existing.hpp"
-
-#include "avdb_scan.hpp"
-#include "avdb_text.hpp"
 
 #include <string.h>
 
@@ -41,12 +37,6 @@ constexpr uint32_t kExistSizeStage = 48 * 1024;
 constexpr uint32_t kExistWriteStage = 32 * 1024;
 constexpr uint32_t kTripRows = 128;
 
-__device__ __forceinline__ void wave_add64(unsigned long long* dst, uint64_t v) {
-  for (int d = 32; d > 0; d >>= 1)
-    v += (uint64_t(uint32_t(__shfl_down(uint32_t(v >> 32), d, kWave))) << 32) | uint32_t(__shfl_down(uint32_t(v), d, kWave));
-  if (__lane_id() == 0 && v) atomicAdd(dst, (unsigned long long)v);
-}
-
 // info[li] = {key_len, pk_len, frag_len, flags | is_row << 8}
 __global__ __launch_bounds__(kBlock) void k_exist_lines(const uint8_t* __restrict__ text, size_t text_bytes,
                                                         const uint64_t* __restrict__ starts, size_t n_lines,
@@ -54,33 +44,17 @@ __global__ __launch_bounds__(kBlock) void k_exist_lines(const uint8_t* __restric
                                                         uint64_t* __restrict__ mark,
                                                         unsigned long long* __restrict__ counts) {
   __shared__ u32x4 s_text[kExistSizeStage / 16];
-  const Heap h = make_heap(text, text_bytes);
   uint64_t n_cr = 0;
-  for (size_t base = size_t(blockIdx.x) * kBlock; base < n_lines; base += size_t(gridDim.x) * kBlock) {
-    const size_t last = base + kBlock < n_lines ? base + kBlock : n_lines;
-    uint64_t s0 = starts[base], s1 = last < n_lines ? starts[last] : text_bytes;
-    if (s0 > text_bytes) s0 = text_bytes;
-    if (s1 > text_bytes || s1 < s0) s1 = text_bytes;
-    const Window w = stage_window<kBlock, kExistSizeStage>(h, s0, s1, s_text);
-    const size_t li = base + threadIdx.x;
-    if (li < n_lines) {
-      uint64_t s, e;
-      bool nl;
-      exist::line_span(text, text_bytes, starts, n_lines, li, &s, &e, &nl);
-      Line L;
-      if (w.staged && s >= s0 && e <= s1)
-        L = exist::scan_line((lds_cp)(reinterpret_cast<const uint8_t*>(s_text) + (h.lo + s - w.a0)), e - s, nl,
-                             contig_mask);
-      else  // a trip longer than the stage
-        L = exist::scan_line((glb_cp)(text + s), e - s, nl, contig_mask);
+  lines::for_each_line<kExistSizeStage>(text, text_bytes, starts, n_lines, s_text, [&](size_t li, auto with_line) {
+    with_line([&](uint64_t, uint64_t len, bool nl, auto line) {
+      const Line L = exist::scan_line(line, len, nl, contig_mask);
       info[li] = u32x4{L.key_len, L.pk_len, L.frag_len, L.flags | (L.is_row << 8)};
       mark[li] = L.is_row;
       n_cr += L.lone_cr;
-    }
-    __syncthreads();  // the stage is reused by the next trip
-  }
+    });
+  });
   if (blockIdx.x == 0 && threadIdx.x == 0) mark[n_lines] = 0;  // the scan leaves the row count there
-  wave_add64(&counts[AVDB_EXIST_COUNT_LONE_CR], n_cr);
+  lines::wave_add(&counts[AVDB_EXIST_COUNT_LONE_CR], n_cr);
 }
 
 __global__ __launch_bounds__(kBlock) void k_exist_compact(const uint64_t* __restrict__ starts, size_t text_bytes,
@@ -113,11 +87,11 @@ __global__ __launch_bounds__(kBlock) void k_exist_compact(const uint64_t* __rest
     counts[AVDB_EXIST_COUNT_ROWS] = rows;
     counts[AVDB_EXIST_COUNT_SKIPPED] = n_lines - rows;
   }
-  wave_add64(&counts[AVDB_EXIST_COUNT_KEY_BYTES], kb);
-  wave_add64(&counts[AVDB_EXIST_COUNT_PK_BYTES], pb);
-  wave_add64(&counts[AVDB_EXIST_COUNT_FRAG_BYTES], fb);
-  wave_add64(&counts[AVDB_EXIST_COUNT_FRAG_HOST], n_host);
-  wave_add64(&counts[AVDB_EXIST_COUNT_NONCANON], n_non);
+  lines::wave_add(&counts[AVDB_EXIST_COUNT_KEY_BYTES], kb);
+  lines::wave_add(&counts[AVDB_EXIST_COUNT_PK_BYTES], pb);
+  lines::wave_add(&counts[AVDB_EXIST_COUNT_FRAG_BYTES], fb);
+  lines::wave_add(&counts[AVDB_EXIST_COUNT_FRAG_HOST], n_host);
+  lines::wave_add(&counts[AVDB_EXIST_COUNT_NONCANON], n_non);
 }
 
 struct ExistOut {
@@ -221,9 +195,8 @@ __global__ __launch_bounds__(kBlock) void k_exist_write(const uint8_t* __restric
     }
     // the trip's text: from its first row's line to the line of the next trip's
     // first row (the skipped lines between rows ride along)
-    uint64_t s0 = row_start[r0], s1 = r0 + nr < n_rows ? row_start[r0 + nr] : text_bytes;
-    if (s0 > text_bytes) s0 = text_bytes;
-    if (s1 > text_bytes || s1 < s0) s1 = text_bytes;
+    uint64_t s0, s1;
+    lines::trip_span(row_start, r0, r0 + nr, n_rows, text_bytes, &s0, &s1);
     const Window w = stage_window<kBlock, kExistWriteStage>(h, s0, s1, s_text);  // (ends in a barrier)
     const lds_cp lds = (lds_cp)(reinterpret_cast<const uint8_t*>(s_text));
     const uint32_t lds0 = uint32_t(h.lo + s0 - w.a0);
@@ -243,20 +216,16 @@ __global__ __launch_bounds__(kBlock) void k_exist_write(const uint8_t* __restric
 
 using namespace avdb;
 
-static size_t pad256(size_t x) { return (x + 255) & ~size_t(255); }
-
-// workspace: count workspace | line starts | marks / row numbers | line info | scan temp
-struct ExistLayout {
-  size_t starts, row_of, info, scan, scan_bytes, total;
+// workspace: lines::Layout | line info | scan temp
+struct ExistLayout : lines::Layout {
+  size_t info, total;
 };
 static ExistLayout exist_layout(size_t n_lines) {
-  ExistLayout L;
-  L.starts = AVDB_VCF_COUNT_WORKSPACE_BYTES;
-  L.row_of = L.starts + pad256(8 * n_lines);
-  L.info = L.row_of + pad256(8 * (n_lines + 1));
-  L.scan = L.info + pad256(16 * n_lines);
+  ExistLayout L{lines::layout(n_lines)};
+  L.info = L.next;
+  L.scan = L.info + lines::pad256(16 * n_lines);
   const size_t a = scan::workspace_bytes(n_lines + 1), b = scan::workspace_bytes(n_lines, 3);
-  L.scan_bytes = pad256(a > b ? a : b);
+  L.scan_bytes = lines::pad256(a > b ? a : b);
   L.total = L.scan + L.scan_bytes;
   return L;
 }
@@ -272,9 +241,7 @@ static const char* size_args_error(const void* ctx, const uint8_t* text, size_t 
                                    const uint32_t* key_len, const uint32_t* pk_len, const uint32_t* frag_len,
                                    const uint8_t* flags, const uint64_t* row_off, const uint64_t* counts) {
   if (!ctx || !counts) return "null argument";
-  if (text_bytes && !text) return "null text";
-  if (n_lines >= 0x7FFFFFFFull) return "too many lines (rows are numbered in int32)";
-  if (n_lines > text_bytes) return "more lines than text bytes";
+  if (const char* err = lines::text_args_error(text, text_bytes, n_lines)) return err;
   if (n_lines && (!key_len || !pk_len || !frag_len || !flags || !row_off)) return "null output array";
   return nullptr;
 }
@@ -294,15 +261,6 @@ static const char* write_args_error(const void* ctx, const uint8_t* text, size_t
   return nullptr;
 }
 
-static int workspace_error(const char* fn, size_t n_lines, const void* workspace, size_t workspace_bytes) {
-  const ExistLayout L = exist_layout(n_lines);
-  if (n_lines && (!workspace || workspace_bytes < L.total || reinterpret_cast<uintptr_t>(workspace) % 256)) {
-    avdb_set_error("%s: 256-byte aligned workspace of %zu bytes required", fn, L.total);
-    return AVDB_ERANGE;
-  }
-  return AVDB_OK;
-}
-
 extern "C" int avdb_existing_size(avdb_ctx* ctx, const uint8_t* text, size_t text_bytes, size_t n_lines,
                                   uint32_t contig_mask, uint32_t* key_len, uint32_t* pk_len, uint32_t* frag_len,
                                   uint8_t* flags, uint64_t* row_off, uint64_t* counts, void* workspace,
@@ -312,28 +270,24 @@ extern "C" int avdb_existing_size(avdb_ctx* ctx, const uint8_t* text, size_t tex
     avdb_set_error("avdb_existing_size: %s", err);
     return AVDB_EINVAL;
   }
-  if (int e = workspace_error("avdb_existing_size", n_lines, workspace, workspace_bytes)) return e;
+  const ExistLayout L = exist_layout(n_lines);
+  if (int e = n_lines ? lines::workspace_error("avdb_existing_size", L.total, workspace, workspace_bytes) : 0) return e;
   AVDB_HIP_TRY(hipSetDevice(ctx->device));
   hipStream_t s = static_cast<hipStream_t>(stream);
   AVDB_HIP_TRY(hipMemsetAsync(counts, 0, 8 * AVDB_EXIST_N_COUNTS, s));
   if (n_lines == 0) return AVDB_OK;
-  const ExistLayout L = exist_layout(n_lines);
   char* w = static_cast<char*>(workspace);
-  auto* starts = reinterpret_cast<uint64_t*>(w + L.starts);
-  auto* row_of = reinterpret_cast<uint64_t*>(w + L.row_of);
   auto* info = reinterpret_cast<u32x4*>(w + L.info);
   auto* cnt = reinterpret_cast<unsigned long long*>(counts);
-  // a start the starts pass does not write (n_lines above the text's own count)
-  // stays past the text: line_span reads such a line as empty
-  AVDB_HIP_TRY(hipMemsetAsync(starts, 0xFF, 8 * n_lines, s));
-  if (int e = text_line_starts(text, text_bytes, n_lines, w, starts, s)) return e;
   const unsigned grid = stream_grid(n_lines, kBlock, 4096);
-  hipLaunchKernelGGL(k_exist_lines, dim3(grid), dim3(kBlock), 0, s, text, text_bytes, starts, n_lines, contig_mask,
-                     info, row_of, cnt);
-  AVDB_LAUNCH_CHECK("k_exist_lines");
-  if (int e = scan::exclusive_u64(row_of, row_of, n_lines + 1, w + L.scan, L.scan_bytes, s)) return e;
-  hipLaunchKernelGGL(k_exist_compact, dim3(grid), dim3(kBlock), 0, s, starts, text_bytes, n_lines, info, row_of,
-                     key_len, pk_len, frag_len, flags, row_off, cnt);
+  auto mark = [&](const uint64_t* starts, uint64_t* marks) {
+    hipLaunchKernelGGL(k_exist_lines, dim3(grid), dim3(kBlock), 0, s, text, text_bytes, starts, n_lines, contig_mask,
+                       info, marks, cnt);
+  };
+  if (int e = lines::number_rows(text, text_bytes, n_lines, w, L, s, "k_exist_lines", mark)) return e;
+  hipLaunchKernelGGL(k_exist_compact, dim3(grid), dim3(kBlock), 0, s, reinterpret_cast<const uint64_t*>(w + L.starts),
+                     text_bytes, n_lines, info, reinterpret_cast<const uint64_t*>(w + L.row_of), key_len, pk_len,
+                     frag_len, flags, row_off, cnt);
   AVDB_LAUNCH_CHECK("k_exist_compact");
   return AVDB_OK;
 }
@@ -351,10 +305,10 @@ extern "C" int avdb_existing_write(avdb_ctx* ctx, const uint8_t* text, size_t te
     avdb_set_error("avdb_existing_write: %s", err);
     return AVDB_EINVAL;
   }
-  if (int e = workspace_error("avdb_existing_write", n_lines, workspace, workspace_bytes)) return e;
+  const ExistLayout L = exist_layout(n_lines);
+  if (int e = n_lines ? lines::workspace_error("avdb_existing_write", L.total, workspace, workspace_bytes) : 0) return e;
   AVDB_HIP_TRY(hipSetDevice(ctx->device));
   hipStream_t s = static_cast<hipStream_t>(stream);
-  const ExistLayout L = exist_layout(n_lines);
   char* w = static_cast<char*>(workspace);
   if (n_rows) {
     scan::Arrays<uint32_t, 3> A{{key_len, pk_len, frag_len}, {key_off, pk_off, frag_off}};
@@ -380,17 +334,12 @@ extern "C" int avdb_existing_size_host(const avdb_ctx* ctx, const uint8_t* text,
   }
   memset(counts, 0, 8 * AVDB_EXIST_N_COUNTS);
   if (n_lines == 0) return AVDB_OK;
-  // line 0 starts at 0, line k + 1 after the k-th newline (as k_vcf_starts)
-  std::vector<uint64_t> starts(n_lines, ~0ull);
-  starts[0] = 0;
-  size_t k = 1;
-  for (size_t i = 0; i < text_bytes && k < n_lines; ++i)
-    if (text[i] == '\n') starts[k++] = i + 1;
+  const std::vector<uint64_t> starts = lines::host_line_starts(text, text_bytes, n_lines);
   uint64_t rows = 0;
   for (size_t li = 0; li < n_lines; ++li) {
     uint64_t s, e;
     bool nl;
-    exist::line_span(text, text_bytes, starts.data(), n_lines, li, &s, &e, &nl);
+    lines::line_span(text, text_bytes, starts.data(), n_lines, li, &s, &e, &nl);
     const Line L = exist::scan_line(text + s, e - s, nl, contig_mask);
     counts[AVDB_EXIST_COUNT_LONE_CR] += L.lone_cr;
     if (!L.is_row) continue;

@@ -1,10 +1,10 @@
 // K12 — per-line and per-row code of the --skipExisting key-set build from an
 // export of AnnotatedVDB.Variant, shared by the kernels (avdb_existing.hip) and the
 // library's host entries (avdb_existing_size_host / avdb_existing_write_host): one
-// definition, compiled for both sides, as avdb_cadd.hpp is.
+// definition, compiled for both sides, as avdb_cadd.hpp is (line spans: avdb_lines.hpp).
 #pragma once
 
-#include "avdb_internal.hpp"
+#include "avdb_lines.hpp"
 
 namespace avdb {
 namespace exist {
@@ -33,27 +33,6 @@ struct Row {
   uint64_t start;
   uint32_t key_len, pk_len, frag_len, flags;
 };
-
-// line li of the text is bytes [*s, *e) without its '\n'; *nl: a '\n' ends it.
-// starts[] comes from the line-starts pass; a start the caller's n_lines does not
-// bear out gives an empty span, so nothing is read outside the text.
-AVDB_HD void line_span(const uint8_t* text, uint64_t text_bytes, const uint64_t* starts, uint64_t n_lines, uint64_t li,
-                       uint64_t* s, uint64_t* e, bool* nl) {
-  uint64_t a = starts[li];
-  const bool last = li + 1 >= n_lines || starts[li + 1] > text_bytes;
-  uint64_t b = last ? text_bytes : starts[li + 1] - 1;
-  if (a > text_bytes) a = text_bytes;
-  if (b > text_bytes) b = text_bytes;
-  if (b < a) b = a;
-  bool has_nl = !last;
-  if (last && b > a && text[b - 1] == '\n') {  // the last line's own newline
-    --b;
-    has_nl = true;
-  }
-  *s = a;
-  *e = b;
-  *nl = has_nl;
-}
 
 // the contig label's bit in the mask: canonical label c -> c, any other -> kOtherBit
 template <class CP>

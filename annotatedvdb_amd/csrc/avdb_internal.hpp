@@ -318,10 +318,6 @@ void keyed_prep_layout(const avdb_ctx* ctx, size_t n, unsigned* grid, size_t* sl
 void keyed_onepass_dd_layout(size_t n, unsigned* grid, size_t* slice);
 // K4 workspace: the per-record bucket codes the keyed K2 fills (avdb_digest.hip)
 uint8_t* vrs_long_codes_of(void* workspace, size_t n);
-// K0's count pass + line-starts pass over any '\n'-separated text (avdb_vcf.hip):
-// starts[0 .. n_lines); count_ws of AVDB_VCF_COUNT_WORKSPACE_BYTES bytes
-int text_line_starts(const uint8_t* text, size_t text_bytes, size_t n_lines, void* count_ws, uint64_t* starts,
-                     hipStream_t s);
 // K4's per-(contig, digit count) SequenceLocation block-1 table (host)
 void location_tail_table(const char* digests, int n_chrom, std::vector<uint64_t>& out);
 }  // namespace avdb

@@ -26,6 +26,7 @@
 #include "avdb_fmt.hpp"
 #include "avdb_vcfline.hpp"
 
+#include "avdb_lines.hpp"  // text_line_starts' declaration
 #include "avdb_scan.hpp"
 
 namespace avdb {

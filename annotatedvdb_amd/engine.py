@@ -1359,7 +1359,7 @@ class Engine:
             N.ptr(counters), self._stream()))
         return match[:n]
 
-    # -- K12: the key set's columns from an export --------------------------------
+    # -- text slabs (K10, K12) ---------------------------------------------------
     def _as_text(self, text) -> torch.Tensor:
         if isinstance(text, (bytes, bytearray, memoryview)):
             text = torch.from_numpy(np.frombuffer(bytes(text), dtype=np.uint8).copy()) if len(text) else \
@@ -1375,6 +1375,20 @@ class Engine:
         first = torch.cumsum(length, 0) - length
         return torch.repeat_interleave(start - first, length) + torch.arange(int(length.sum()), device=start.device)
 
+    def _count_lines(self, text: torch.Tensor) -> int:
+        """Lines of a '\\n'-separated slab: newlines + (the text does not end in one)."""
+        nb = text.numel()
+        if nb == 0:
+            return 0
+        if self.host_only:
+            return int((text == 10).sum()) + int(text[-1] != 10)
+        ws = self.scratch("text_count", N.VCF_COUNT_WORKSPACE_BYTES)
+        cnt = self.empty(1, torch.int64)
+        N.check("avdb_vcf_count_lines", self.lib.avdb_vcf_count_lines(
+            self.ctx, N.ptr(text), nb, N.ptr(ws), ws.numel(), N.ptr(cnt), self._stream()))
+        return int(cnt.item()) + int(text[-1].item() != 10)
+
+    # -- K12: the key set's columns from an export --------------------------------
     def existing_table_build(self, text, contigs=None) -> "ExistingColumns":
         """K12: a slab of an export of ``AnnotatedVDB.Variant``
         (``metaseq_id<TAB>record_primary_key<TAB>bin_index[<TAB>...]`` lines; bytes,
@@ -1455,30 +1469,12 @@ class Engine:
         """``{snv, indel, not_matched}`` (``N.CADD_CTR_*``), added to by :meth:`cadd_match`."""
         return torch.zeros(N.CADD_N_CTRS, dtype=torch.int64, device=self.device)
 
-    def _count_lines(self, text: torch.Tensor) -> int:
-        """Lines of a '\\n'-separated slab: newlines + (the text does not end in one)."""
-        nb = text.numel()
-        if nb == 0:
-            return 0
-        if self.host_only:
-            return int((text == 10).sum()) + int(text[-1] != 10)
-        ws = self.scratch("cadd_count", N.VCF_COUNT_WORKSPACE_BYTES)
-        cnt = self.empty(1, torch.int64)
-        N.check("avdb_vcf_count_lines", self.lib.avdb_vcf_count_lines(
-            self.ctx, N.ptr(text), nb, N.ptr(ws), ws.numel(), N.ptr(cnt), self._stream()))
-        return int(cnt.item()) + int(text[-1].item() != 10)
-
     def cadd_table_build(self, text) -> "CaddColumns":
         """K10a: a slab of uncompressed CADD TSV (bytes, numpy ``uint8`` or a ``uint8``
         tensor) -> the table's columns on this engine's device.  One sync (the line
         count) before the build, one after (the counts).  On a host-only engine the
         library's host entry runs the same per-line code."""
-        if isinstance(text, (bytes, bytearray, memoryview)):
-            text = torch.from_numpy(np.frombuffer(bytes(text), dtype=np.uint8).copy()) if len(text) else \
-                torch.zeros(0, dtype=torch.uint8)
-        elif isinstance(text, np.ndarray):
-            text = torch.from_numpy(np.ascontiguousarray(text, dtype=np.uint8))
-        text = self._dev(text)
+        text = self._as_text(text)
         nb = text.numel()
         n_lines = self._count_lines(text)
         m = max(1, n_lines)

@@ -37,7 +37,6 @@ with no Python object per row.
 from __future__ import annotations
 
 import ast
-import gzip
 import os
 from typing import Dict, Iterable, List, Optional, Sequence, Tuple
 
@@ -115,7 +114,8 @@ class ExistingVariants(object):
         eng = engine or default_engine()
         text = path_or_text
         if isinstance(text, (str, os.PathLike)):
-            text = cls._read_export(os.fspath(text), eng)
+            from . import bgzf
+            text = bgzf.read_whole(os.fspath(text), eng)
         self = cls.__new__(cls)
         self._engine = eng
         self.check_alt = check_alt
@@ -125,19 +125,6 @@ class ExistingVariants(object):
         self.frag, self.frag_off = c.frag, c.frag_off
         self.table = eng.keyset_build(c.keys, c.key_off)
         return self
-
-    @staticmethod
-    def _read_export(path: str, eng):
-        from . import bgzf
-        if bgzf.is_bgzf(path):
-            try:
-                return bgzf.BgzfFile(path, eng).read()
-            except bgzf.NotBgzf:
-                pass
-        with open(path, "rb") as fh:
-            magic = fh.read(2)
-        with (gzip.open if magic == b"\x1f\x8b" else open)(path, "rb") as fh:
-            return fh.read()
 
     def _row_bytes(self, blob: torch.Tensor, off: torch.Tensor, k: int) -> bytes:
         a, b = off[k:k + 2].tolist()

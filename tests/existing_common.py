@@ -192,3 +192,74 @@ def h4() -> bytes:
         if i % 97 == 0:
             out.append(b"junk\n")
     return b"".join(out)
+
+
+# ---- texts on the size pass's stage fit boundary -------------------------------
+TRIP = 256          # lines per k_exist_lines trip (one workgroup); a skipped line is a line
+STAGE = 48 * 1024   # its LDS stage: a trip is staged when its span, counted from the
+#                     16-byte floor of its first line's address, is at most this
+LONG_TRIP = "long"  # a trip holding one line with a 60,000-byte metaseq id
+JUNK = b"~\t~\t~\n"   # a row of three fields in 6 bytes, of a byte no text here has
+
+
+def fit_line(i, fill=0):
+    """Row i with ``fill`` more bytes in its bin; every 4th row has further columns,
+    every 9th ends in "\\r\\n", every 50th has a primary key repr() escapes in."""
+    pk = b"it's:%d" % i if i % 50 == 7 else b"%d:%d:A:G:rs%d" % (i % 22 + 1, 1000 + i, i)
+    return b"%d:%d:A:G\t%s\tchr%d.L1.B%d%s%s%s\n" % (i % 22 + 1, 1000 + i, pk, i % 22 + 1, i % 9, b"f" * fill,
+                                                b"\tmore\tcolumns" if i % 4 == 1 else b"", b"\r" if i % 9 == 4 else b"")
+
+
+def fit_text(spans, residue=0, tail_lines=100):
+    """Text whose trip k stages exactly ``spans[k]`` bytes on a slab at ``residue``
+    mod 16, then ``tail_lines`` plain rows, the last without newline.  A skipped line
+    is the first line of every odd trip and the last line of every even one."""
+    out, at, i = [], 0, 0
+    for t, span in enumerate(spans):
+        lines = [fit_line(i + k) for k in range(TRIP)]
+        lines[0 if t % 2 else TRIP - 1] = b"metaseq_id\trecord_primary_key\tbin_index\n" if t % 4 < 2 else b"two\tfields\n"
+        if span == LONG_TRIP:
+            lines[100] = b"1:%d:%s:T\tlong%d\tchr1.L1.B1\n" % (i + 100, b"ACGT" * 15000, i)
+        else:
+            room = span - ((at + residue) & 15) - sum(len(ln) for ln in lines)
+            assert room >= 0
+            q, r = divmod(room, TRIP - 2)  # shared by the lines between the first and the last
+            for k in range(1, TRIP - 1):
+                lines[k] = fit_line(i + k, q + (k <= r))
+        out += lines
+        at += sum(len(ln) for ln in lines)
+        i += TRIP
+    out += [fit_line(i + k, k % 5) for k in range(tail_lines)]
+    return b"".join(out)[:-1]
+
+
+def fit_plan(first):
+    """Trip 0 at ``first`` bytes, then fitting and non-fitting trips in turn."""
+    rest = [STAGE + 1, STAGE, LONG_TRIP, STAGE - 16, STAGE + 16] if first <= STAGE else \
+        [STAGE, STAGE + 1, STAGE - 16, LONG_TRIP, STAGE, STAGE + 16]
+    return [first] + rest
+
+
+def trip_spans(text, residue=0):
+    """Per trip of 256 lines, the bytes k_exist_lines would stage for a slab whose
+    address is ``residue`` mod 16, computed from the text alone."""
+    a = np.frombuffer(text, dtype=np.uint8)
+    starts = np.concatenate(([0], np.flatnonzero(a == 10) + 1))
+    if starts[-1] == len(text):
+        starts = starts[:-1]  # the text ends in its last line's newline
+    s0 = starts[::TRIP]
+    s1 = np.concatenate((s0[1:], [len(text)]))
+    return (s1 + residue) - ((s0 + residue) & ~np.int64(15))
+
+
+def check_fit_plan(text, plan, residue=0):
+    spans = trip_spans(text, residue).tolist()
+    assert len(spans) == len(plan) + 1 and spans[-1] < STAGE
+    assert [s for s, p in zip(spans, plan) if p != LONG_TRIP] == [p for p in plan if p != LONG_TRIP], spans
+    assert all(s > 60000 for s, p in zip(spans, plan) if p == LONG_TRIP)
+    fits = [s <= STAGE for s in spans]
+    assert all(a != b for a, b in zip(fits, fits[1:])), fits  # staged and unstaged trips alternate
+    lines = text.split(b"\n")
+    skipped = [ln.count(b"\t") < 2 or ln.startswith(b"metaseq_id\t") for ln in lines]
+    assert all(skipped[t * TRIP + (0 if t % 2 else TRIP - 1)] for t in range(len(plan))) and not text.endswith(b"\n")
+    return fits

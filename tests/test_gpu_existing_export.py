@@ -55,6 +55,57 @@ def test_g1_lone_cr_raises(engine):
         engine.existing_table_build(b"a\rb\n1:1:A:C\tpk\tbin\r")
 
 
+# ---- G1b: the size pass's stage fit boundary, as tests/test_gpu_cadd_edges.py e2 / e3 ---
+def check_columns(engine, host, text, slab=None):
+    """The device columns of ``text`` (or of ``slab``, a device tensor holding it), under
+    poison, against the host entries, and both against the restatement."""
+    want, ref = X.restate(text), X.columns(host, text)
+    engine.poison = 0xA5
+    try:
+        dev = X.columns(engine, text if slab is None else slab)
+    finally:
+        engine.poison = None
+    X.assert_same(ref, want)
+    X.assert_same(dev, want)
+    X.assert_same(dev, ref)
+    return dev
+
+
+@pytest.mark.parametrize("first", [49136, 49152, 49153, 49168])
+def test_g1_size_pass_stage_fit_boundary(engine, host, first):
+    """Trip 0 of k_exist_lines stages 49,136 / 49,152 bytes (the last that fits
+    kExistSizeStage) or is read from global memory at 49,153 / 49,168; the trips after it
+    alternate, one of them holds a line longer than the whole stage, a skipped line is
+    the first or the last of every trip, the last line has no newline."""
+    plan = X.fit_plan(first)
+    text = X.fit_text(plan)
+    fits = X.check_fit_plan(text, plan)
+    assert fits[0] == (first <= X.STAGE) and 300000 < len(text) < 450000
+    slab = torch.from_numpy(np.frombuffer(text, dtype=np.uint8).copy()).to(engine.device)
+    assert slab.data_ptr() % 16 == 0
+    dev = check_columns(engine, host, text, slab)
+    assert dev["counts"]["rows"] == len(plan) * (X.TRIP - 1) + 100 and dev["counts"]["skipped"] == len(plan)
+    assert int(np.diff(dev["key_off"]).max()) > 60000 and dev["counts"]["frag_host"] > 30
+
+
+@pytest.mark.parametrize("k", [1, 7, 8, 15])
+def test_g1_unaligned_slab(engine, host, k):
+    """The slab ``k`` bytes off 16-byte alignment, row-shaped junk before and after it:
+    the stage's first word starts before the text, and the fit boundary moves with the
+    address — the text is built for this residue, so 49,152 / 49,153 are again exact."""
+    plan = X.fit_plan(X.STAGE if k % 2 else X.STAGE + 1)
+    text = X.fit_text(plan, residue=k)
+    X.check_fit_plan(text, plan, residue=k)
+    whole = (X.JUNK * 3)[-k:] + text + X.JUNK * 12
+    dev_whole = torch.from_numpy(np.frombuffer(whole, dtype=np.uint8).copy()).to(engine.device)
+    assert dev_whole.data_ptr() % 16 == 0 and whole[:k].endswith(b"\n") and b"~" not in text
+    assert k < 7 or X.restate(whole[:k])["counts"]["rows"] >= 1  # the junk before the text is a row
+    slab = dev_whole[k:k + len(text)]
+    assert slab.is_contiguous() and slab.data_ptr() % 16 == k
+    dev = check_columns(engine, host, text, slab)
+    assert not any(b"~" in dev[name] for name in ("keys", "pks", "frag"))
+
+
 # ---- G2: a seeded export -----------------------------------------------------------
 def _lines(n, seed):
     from annotatedvdb_amd import synth
