@@ -237,9 +237,7 @@ __global__ __launch_bounds__(kK1Block) void k_bin_assign4(
   }
   if (ctrs) {
     flush_errors(err, s_ctr);
-    // records per workgroup: wave reduce, one LDS atomic per wave
-    for (int d = 32; d > 0; d >>= 1) nrec += __shfl_down(nrec, d, kWave);
-    if (__lane_id() == 0 && nrec) atomicAdd(&s_ctr[AVDB_CTR_RECORDS], (unsigned long long)nrec);
+    wave_add(&s_ctr[AVDB_CTR_RECORDS], nrec);  // records per workgroup: one LDS atomic per wave
     __syncthreads();
     if (threadIdx.x == 0) {
       const unsigned long long bad = s_ctr[AVDB_CTR_STATUS0 + 1] + s_ctr[AVDB_CTR_STATUS0 + 2] +
@@ -556,8 +554,7 @@ __global__ __launch_bounds__(kK1Block, KEYS == 2 ? 6 : 1) void k_record_prep4(
           uint32_t pc = __shfl_up(c4 >> 24, 1, kWave), pp = __shfl_up(q4.w, 1, kWave);
           uint32_t pr = __shfl_up(rr.w, 1, kWave), pa = __shfl_up(aa.w, 1, kWave);
           const uint64_t e3 = x23[u][1];
-          uint64_t pe = (uint64_t(uint32_t(__shfl_up(uint32_t(e3 >> 32), 1, kWave))) << 32) |
-                        uint32_t(__shfl_up(uint32_t(e3), 1, kWave));
+          uint64_t pe = shfl_up64(e3, 1);
           uint32_t same = 0;
           if (live) {
             same |= uint32_t(((c4 >> 8) & 0xFFu) == (c4 & 0xFFu) && q4.y == q4.x) << 1;
@@ -581,20 +578,8 @@ __global__ __launch_bounds__(kK1Block, KEYS == 2 ? 6 : 1) void k_record_prep4(
           cand |= uint32_t(rr.z == rr.y && aa.z == aa.y && x23[u][0] == x01[u][1]) << 2;
           cand |= uint32_t(rr.w == rr.z && aa.w == aa.z && x23[u][1] == x23[u][0]) << 3;
           same &= cand | prev_same;
-          const uint32_t cnt = __popc(same);
-          uint32_t incl = cnt;
-#pragma unroll
-          for (int d = 1; d < kWave; d <<= 1) {
-            const uint32_t up = __shfl_up(incl, d, kWave);
-            if (__lane_id() >= uint32_t(d)) incl += up;
-          }
-          const uint32_t total = __shfl(incl, kWave - 1, kWave);
-          if (total) {
-            uint32_t at = 0;
-            if (__lane_id() == kWave - 1) at = atomicAdd(&s_dd, total);
-            at = __shfl(at, kWave - 1, kWave) + incl - cnt;
-            for (uint32_t m = same; m; m &= m - 1) dd_mine[at++] = uint32_t(4 * j + __builtin_ctz(m));
-          }
+          uint32_t at = wave_append(__popc(same), &s_dd);
+          for (uint32_t m = same; m; m &= m - 1) dd_mine[at++] = uint32_t(4 * j + __builtin_ctz(m));
           if (live) reinterpret_cast<uint32_t*>(kt.keep)[j] = 0x01010101u;
         }
         if (kt.long_codes && live) {
@@ -645,8 +630,7 @@ __global__ __launch_bounds__(kK1Block, KEYS == 2 ? 6 : 1) void k_record_prep4(
   }
   if (ctrs) {
     flush_errors(err, s_ctr);
-    for (int d = 32; d > 0; d >>= 1) nrec += __shfl_down(nrec, d, kWave);
-    if (__lane_id() == 0 && nrec) atomicAdd(&s_ctr[AVDB_CTR_RECORDS], (unsigned long long)nrec);
+    wave_add(&s_ctr[AVDB_CTR_RECORDS], nrec);
     __syncthreads();
     if (threadIdx.x == 0) {
       const unsigned long long bad = s_ctr[AVDB_CTR_STATUS0 + 1] + s_ctr[AVDB_CTR_STATUS0 + 2] +

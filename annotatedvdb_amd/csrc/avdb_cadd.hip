@@ -58,8 +58,8 @@ __global__ __launch_bounds__(kBlock) void k_cadd_parse(const uint8_t* __restrict
     });
   });
   if (blockIdx.x == 0 && threadIdx.x == 0) counts[AVDB_CADD_COUNT_ROWS] = row_of[n_lines];
-  lines::wave_add(&counts[AVDB_CADD_COUNT_SCORE_HOST], n_host);
-  lines::wave_add(&counts[AVDB_CADD_COUNT_BAD], n_bad);
+  wave_add(&counts[AVDB_CADD_COUNT_SCORE_HOST], n_host);
+  wave_add(&counts[AVDB_CADD_COUNT_BAD], n_bad);
 }
 
 // runs: u32[kContigs] run starts seen per contig (zeroed by the caller)
@@ -83,7 +83,7 @@ __global__ __launch_bounds__(kBlock) void k_cadd_index(const uint8_t* __restrict
       if (ev.end) atomicMax(&end_row[ev.contig], uint32_t(i + 1));
     }
   }
-  lines::wave_add(&counts[AVDB_CADD_COUNT_ORDER_VIOLATIONS], viol);
+  wave_add(&counts[AVDB_CADD_COUNT_ORDER_VIOLATIONS], viol);
 }
 
 __global__ __launch_bounds__(kBlock) void k_cadd_match(View snv, View indel, const uint8_t* __restrict__ chrom,
@@ -110,9 +110,9 @@ __global__ __launch_bounds__(kBlock) void k_cadd_match(View snv, View indel, con
     n_none += k == AVDB_CADD_NONE;
   }
   if (ctr) {
-    lines::wave_add(&ctr[AVDB_CADD_CTR_SNV], n_snv);
-    lines::wave_add(&ctr[AVDB_CADD_CTR_INDEL], n_indel);
-    lines::wave_add(&ctr[AVDB_CADD_CTR_NOT_MATCHED], n_none);
+    wave_add(&ctr[AVDB_CADD_CTR_SNV], n_snv);
+    wave_add(&ctr[AVDB_CADD_CTR_INDEL], n_indel);
+    wave_add(&ctr[AVDB_CADD_CTR_NOT_MATCHED], n_none);
   }
 }
 

@@ -111,8 +111,7 @@ __device__ __forceinline__ uint8_t dedup_record(const Heap& h, const uint8_t* __
 
 __device__ __forceinline__ void count_dups(uint32_t dups, unsigned long long* g_ctr) {
   if (!g_ctr) return;
-  for (int d = 32; d > 0; d >>= 1) dups += __shfl_down(dups, d, kWave);
-  if (__lane_id() == 0 && dups) atomicAdd(&g_ctr[AVDB_CTR_DUPLICATES], (unsigned long long)dups);
+  wave_add(&g_ctr[AVDB_CTR_DUPLICATES], dups);
 }
 
 __global__ __launch_bounds__(kBlock) void k_dedup_grouped(
@@ -298,20 +297,8 @@ __global__ __launch_bounds__(kBlock) void k_dedup_mark4(const uint8_t* __restric
     same |= uint32_t((c4 >> 24) == ((c4 >> 16) & 0xFFu) && p4.w == p4.z) << 3;
     if (!full) same &= (live && i0 < n) ? (1u << uint32_t(n - i0 < 4 ? n - i0 : 4)) - 1u : 0u;
     // wave-aggregated append of this lane's suspects to the workgroup's slice
-    const uint32_t cnt = __popc(same);
-    uint32_t incl = cnt;
-#pragma unroll
-    for (int d = 1; d < kWave; d <<= 1) {
-      const uint32_t u = __shfl_up(incl, d, kWave);
-      if (__lane_id() >= d) incl += u;
-    }
-    const uint32_t total = __shfl(incl, kWave - 1, kWave);
-    if (total) {
-      uint32_t at = 0;
-      if (__lane_id() == kWave - 1) at = atomicAdd(&s_cnt, total);
-      at = __shfl(at, kWave - 1, kWave) + incl - cnt;
-      for (uint32_t m = same; m; m &= m - 1) mine[at++] = uint32_t(i0 + __builtin_ctz(m));
-    }
+    uint32_t at = wave_append(__popc(same), &s_cnt);
+    for (uint32_t m = same; m; m &= m - 1) mine[at++] = uint32_t(i0 + __builtin_ctz(m));
     if (full) {
       *reinterpret_cast<uint32_t*>(keep + i0) = 0x01010101u;
     } else if (live) {
@@ -447,14 +434,8 @@ __global__ __launch_bounds__(kBlock) void k_dedup_resolve(
     dups += 1u - k;
   }
   if (g_ctr) {
-    for (int d = 32; d > 0; d >>= 1) {
-      dups += __shfl_down(dups, d, kWave);
-      coll += __shfl_down(coll, d, kWave);
-    }
-    if (__lane_id() == 0) {
-      if (dups) atomicAdd(&g_ctr[AVDB_CTR_DUPLICATES], (unsigned long long)dups);
-      if (coll) atomicAdd(&g_ctr[AVDB_CTR_HASH_COLLISIONS], (unsigned long long)coll);
-    }
+    wave_add(&g_ctr[AVDB_CTR_DUPLICATES], dups);
+    wave_add(&g_ctr[AVDB_CTR_HASH_COLLISIONS], coll);
   }
 }
 

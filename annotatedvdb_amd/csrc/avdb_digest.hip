@@ -363,16 +363,6 @@ constexpr uint32_t kScanN = kLongBuckets * kCompactGrid;
 constexpr uint32_t kScanSteps = kScanN / 16 / 256;
 static_assert(kScanN % (16 * 256) == 0, "k_long_scan layout");
 
-__device__ __forceinline__ uint32_t wave_incl_scan(uint32_t v) {
-  const int lane = __lane_id();
-#pragma unroll
-  for (int d = 1; d < kWave; d <<= 1) {
-    const uint32_t u = __shfl_up(v, d, kWave);
-    if (lane >= d) v += u;
-  }
-  return v;
-}
-
 __global__ __launch_bounds__(1024) void k_long_scan(uint32_t* __restrict__ counts,
                                                     unsigned int* __restrict__ total) {
   __shared__ uint32_t s_wave[16];
@@ -384,7 +374,7 @@ __global__ __launch_bounds__(1024) void k_long_scan(uint32_t* __restrict__ count
   uint32_t tot = 0;
 #pragma unroll
   for (uint32_t k = 0; k < kScanSteps; ++k) tot += v[k].x + v[k].y + v[k].z + v[k].w;
-  const uint32_t wsum = __shfl(wave_incl_scan(tot), 63, kWave);
+  const uint32_t wsum = __shfl(wave_incl_sum(tot), 63, kWave);
   if (lane == 0) s_wave[wv] = wsum;
   __syncthreads();
   uint32_t base = 0;
@@ -392,7 +382,7 @@ __global__ __launch_bounds__(1024) void k_long_scan(uint32_t* __restrict__ count
 #pragma unroll
   for (uint32_t k = 0; k < kScanSteps; ++k) {
     const uint32_t ls = v[k].x + v[k].y + v[k].z + v[k].w;
-    const uint32_t incl = wave_incl_scan(ls);
+    const uint32_t incl = wave_incl_sum(ls);
     uint32_t run = base + incl - ls;
     u32x4 o;
     o.x = run; run += v[k].x;

@@ -54,7 +54,7 @@ __global__ __launch_bounds__(kBlock) void k_exist_lines(const uint8_t* __restric
     });
   });
   if (blockIdx.x == 0 && threadIdx.x == 0) mark[n_lines] = 0;  // the scan leaves the row count there
-  lines::wave_add(&counts[AVDB_EXIST_COUNT_LONE_CR], n_cr);
+  wave_add(&counts[AVDB_EXIST_COUNT_LONE_CR], n_cr);
 }
 
 __global__ __launch_bounds__(kBlock) void k_exist_compact(const uint64_t* __restrict__ starts, size_t text_bytes,
@@ -87,11 +87,11 @@ __global__ __launch_bounds__(kBlock) void k_exist_compact(const uint64_t* __rest
     counts[AVDB_EXIST_COUNT_ROWS] = rows;
     counts[AVDB_EXIST_COUNT_SKIPPED] = n_lines - rows;
   }
-  lines::wave_add(&counts[AVDB_EXIST_COUNT_KEY_BYTES], kb);
-  lines::wave_add(&counts[AVDB_EXIST_COUNT_PK_BYTES], pb);
-  lines::wave_add(&counts[AVDB_EXIST_COUNT_FRAG_BYTES], fb);
-  lines::wave_add(&counts[AVDB_EXIST_COUNT_FRAG_HOST], n_host);
-  lines::wave_add(&counts[AVDB_EXIST_COUNT_NONCANON], n_non);
+  wave_add(&counts[AVDB_EXIST_COUNT_KEY_BYTES], kb);
+  wave_add(&counts[AVDB_EXIST_COUNT_PK_BYTES], pb);
+  wave_add(&counts[AVDB_EXIST_COUNT_FRAG_BYTES], fb);
+  wave_add(&counts[AVDB_EXIST_COUNT_FRAG_HOST], n_host);
+  wave_add(&counts[AVDB_EXIST_COUNT_NONCANON], n_non);
 }
 
 struct ExistOut {

@@ -7,6 +7,7 @@
 #include <stddef.h>
 
 #include "../../include/avdb.h"
+#include "avdb_wave.hpp"
 
 namespace avdb {
 
@@ -17,7 +18,6 @@ namespace avdb {
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 typedef uint64_t u64x2 __attribute__((ext_vector_type(2)));
 
-constexpr int kWave = 64;
 constexpr int kBlock = 256;               // 4 waves per workgroup
 constexpr uint32_t kLeafWidth = 15625;    // L13 bin width, generate_bin_index_references.py:93
 constexpr uint32_t kL8Width = 500000;     // L8 bin width (histogram granularity)
@@ -222,8 +222,7 @@ struct ErrCounters {
   // workgroup epilogue: records + derived OK count into s_ctr (before publish)
   __device__ __forceinline__ void finish(unsigned long long* s_ctr) {
     flush_errors(err, s_ctr);
-    for (int d = 32; d > 0; d >>= 1) nrec += __shfl_down(nrec, d, 64);
-    if (__lane_id() == 0 && nrec) atomicAdd(&s_ctr[AVDB_CTR_RECORDS], (unsigned long long)nrec);
+    wave_add(&s_ctr[AVDB_CTR_RECORDS], nrec);
     __syncthreads();
     if (threadIdx.x == 0) {
       const unsigned long long bad = s_ctr[AVDB_CTR_STATUS0 + 1] + s_ctr[AVDB_CTR_STATUS0 + 2] +
@@ -264,19 +263,6 @@ __device__ __forceinline__ uint32_t long_bucket(uint32_t a) {
 }
 __device__ __forceinline__ uint32_t long_code(uint32_t r, uint32_t a, uint32_t max_len) {
   return uint64_t(r) + a > max_len ? 1u + long_bucket(a) : 0u;
-}
-
-// inclusive wave64 prefix sum through DPP row shifts and row broadcasts: six
-// VALU adds with no LDS round trip (__shfl_up lowers to ds_bpermute: six
-// dependent LDS trips per value)
-__device__ __forceinline__ uint32_t wave_incl_sum(uint32_t x) {
-  x += __builtin_amdgcn_update_dpp(0u, x, 0x111, 0xF, 0xF, false);  // row_shr:1
-  x += __builtin_amdgcn_update_dpp(0u, x, 0x112, 0xF, 0xF, false);  // row_shr:2
-  x += __builtin_amdgcn_update_dpp(0u, x, 0x114, 0xF, 0xF, false);  // row_shr:4
-  x += __builtin_amdgcn_update_dpp(0u, x, 0x118, 0xF, 0xF, false);  // row_shr:8
-  x += __builtin_amdgcn_update_dpp(0u, x, 0x142, 0xA, 0xF, false);  // row_bcast:15 into rows 1, 3
-  x += __builtin_amdgcn_update_dpp(0u, x, 0x143, 0xC, 0xF, false);  // row_bcast:31 into rows 2, 3
-  return x;
 }
 
 }  // namespace avdb

@@ -148,18 +148,6 @@ __device__ __forceinline__ void record_sizes(const KeyArgs& A, uint32_t c, uint3
                  A.code != nullptr, ks, ps);
 }
 
-__device__ __forceinline__ uint32_t wave_sum32(uint32_t v) {
-#pragma unroll
-  for (int d = 32; d > 0; d >>= 1) v += __shfl_xor(v, d, kWave);
-  return v;
-}
-__device__ __forceinline__ uint64_t wave_sum64(uint64_t v) {
-#pragma unroll
-  for (int d = 32; d > 0; d >>= 1)
-    v += (uint64_t(uint32_t(__shfl_xor(uint32_t(v >> 32), d, kWave))) << 32) | uint32_t(__shfl_xor(uint32_t(v), d, kWave));
-  return v;
-}
-
 // the (keys, paths) bytes of group g (records (g << group_log2 + k) * 64 + lane),
 // summed over the wave
 __device__ __forceinline__ uint2 group_total(const KeyArgs& A, size_t g, uint32_t lane) {
@@ -176,7 +164,7 @@ __device__ __forceinline__ uint2 group_total(const KeyArgs& A, size_t g, uint32_
       P += ps;
     }
   }
-  return make_uint2(wave_sum32(K), wave_sum32(P));
+  return make_uint2(wave_sum(K), wave_sum(P));
 }
 
 // group totals: one wave per group of 64 << group_log2 records
@@ -198,7 +186,7 @@ __global__ __launch_bounds__(kBlock) void k_key_group_totals(KeyArgs A, uint2* _
 __global__ __launch_bounds__(kScanThreads) void k_key_group_scan(const uint2* __restrict__ tot, size_t n_groups,
                                                                   uint2* __restrict__ pre, uint64_t* __restrict__ btot,
                                                                   KeyArgs A, int redo_last) {
-  __shared__ uint32_t s_k[kScanThreads / kWave], s_p[kScanThreads / kWave];
+  __shared__ uint32_t s_w[2][kScanThreads / kWave];
   __shared__ uint2 s_last;
   const uint32_t lane = __lane_id(), wv = threadIdx.x / kWave;
   const bool redo = redo_last && blockIdx.x == gridDim.x - 1;  // (block-uniform)
@@ -211,37 +199,15 @@ __global__ __launch_bounds__(kScanThreads) void k_key_group_scan(const uint2* __
   }
   const size_t g0 = size_t(blockIdx.x) * kGroupsPerBlock + 4 * threadIdx.x;
   uint2 v[4];
-  uint32_t k = 0, p = 0;
+  uint32_t e[2] = {0, 0}, t[2];  // (keys, paths)
 #pragma unroll
   for (int q = 0; q < 4; ++q) {
     v[q] = g0 + q < n_groups ? (redo && g0 + q == n_groups - 1 ? s_last : tot[g0 + q]) : make_uint2(0, 0);
-    k += v[q].x;
-    p += v[q].y;
+    e[0] += v[q].x;
+    e[1] += v[q].y;
   }
-  uint32_t xk = k, xp = p;
-#pragma unroll
-  for (int d = 1; d < kWave; d <<= 1) {
-    const uint32_t uk = __shfl_up(xk, d, kWave), up = __shfl_up(xp, d, kWave);
-    if (lane >= uint32_t(d)) {
-      xk += uk;
-      xp += up;
-    }
-  }
-  if (lane == kWave - 1) {
-    s_k[wv] = xk;
-    s_p[wv] = xp;
-  }
-  __syncthreads();
-  uint32_t bk = 0, bp = 0, tk = 0, tp = 0;
-  for (uint32_t w = 0; w < kScanThreads / kWave; ++w) {
-    if (w < wv) {
-      bk += s_k[w];
-      bp += s_p[w];
-    }
-    tk += s_k[w];
-    tp += s_p[w];
-  }
-  uint32_t ek = bk + xk - k, ep = bp + xp - p;
+  block_excl<kScanThreads>(e, s_w, t);
+  uint32_t ek = e[0], ep = e[1];
 #pragma unroll
   for (int q = 0; q < 4; ++q) {
     if (g0 + q < n_groups) pre[g0 + q] = make_uint2(ek, ep);
@@ -249,8 +215,8 @@ __global__ __launch_bounds__(kScanThreads) void k_key_group_scan(const uint2* __
     ep += v[q].y;
   }
   if (threadIdx.x == 0) {
-    btot[2 * blockIdx.x] = tk;
-    btot[2 * blockIdx.x + 1] = tp;
+    btot[2 * blockIdx.x] = t[0];
+    btot[2 * blockIdx.x + 1] = t[1];
   }
 }
 
@@ -260,45 +226,18 @@ __global__ __launch_bounds__(kScanThreads) void k_key_block_scan(uint64_t* __res
                                                                  uint64_t* __restrict__ key_off,
                                                                  uint64_t* __restrict__ path_off, size_t n,
                                                                  uint32_t off32) {
-  __shared__ uint64_t s_k[kScanThreads / kWave], s_p[kScanThreads / kWave];
-  const uint32_t lane = __lane_id(), wv = threadIdx.x / kWave;
+  __shared__ uint64_t s_w[2][kScanThreads / kWave];
   uint64_t run_k = 0, run_p = 0;
   for (size_t c0 = 0; c0 < nb; c0 += kScanThreads) {
     const size_t i = c0 + threadIdx.x;
-    const uint64_t k = i < nb ? b[2 * i] : 0ull, p = i < nb ? b[2 * i + 1] : 0ull;
-    uint64_t xk = k, xp = p;
-#pragma unroll
-    for (int d = 1; d < kWave; d <<= 1) {
-      const uint64_t uk = (uint64_t(uint32_t(__shfl_up(uint32_t(xk >> 32), d, kWave))) << 32) |
-                          uint32_t(__shfl_up(uint32_t(xk), d, kWave));
-      const uint64_t up = (uint64_t(uint32_t(__shfl_up(uint32_t(xp >> 32), d, kWave))) << 32) |
-                          uint32_t(__shfl_up(uint32_t(xp), d, kWave));
-      if (lane >= uint32_t(d)) {
-        xk += uk;
-        xp += up;
-      }
-    }
-    if (lane == kWave - 1) {
-      s_k[wv] = xk;
-      s_p[wv] = xp;
-    }
-    __syncthreads();
-    uint64_t bk = 0, bp = 0, tk = 0, tp = 0;
-    for (uint32_t w = 0; w < kScanThreads / kWave; ++w) {
-      if (w < wv) {
-        bk += s_k[w];
-        bp += s_p[w];
-      }
-      tk += s_k[w];
-      tp += s_p[w];
-    }
+    uint64_t e[2] = {i < nb ? b[2 * i] : 0ull, i < nb ? b[2 * i + 1] : 0ull}, t[2];  // (keys, paths)
+    block_excl<kScanThreads>(e, s_w, t);
     if (i < nb) {
-      b[2 * i] = run_k + bk + xk - k;
-      b[2 * i + 1] = run_p + bp + xp - p;
+      b[2 * i] = run_k + e[0];
+      b[2 * i + 1] = run_p + e[1];
     }
-    run_k += tk;
-    run_p += tp;
-    __syncthreads();
+    run_k += t[0];
+    run_p += t[1];
   }
   if (threadIdx.x == 0) {
     if (off32) {
@@ -657,8 +596,8 @@ __global__ __launch_bounds__(kV2Block, AVDB_K7_V2_WAVES) void k_record_keys_v2(K
           bk += A.blk_pre[2 * q];
           bp += A.blk_pre[2 * q + 1];
         }
-        run_k = wave_sum64(bk) + gp.x;
-        run_p = wave_sum64(bp) + gp.y;
+        run_k = wave_sum(bk) + gp.x;
+        run_p = wave_sum(bp) + gp.y;
       } else {
         run_k = A.blk_pre[2 * b] + gp.x;
         run_p = A.blk_pre[2 * b + 1] + gp.y;
@@ -832,8 +771,8 @@ __device__ __forceinline__ void group_lookback(unsigned long long* lb, uint32_t*
       vk += take ? (sk[j] & kLbVal) : 0ull;
       vp += take ? (sp[j] & kLbVal) : 0ull;
     }
-    ek += wave_sum64(vk);
-    ep += wave_sum64(vp);
+    ek += wave_sum(vk);
+    ep += wave_sum(vp);
     if (inc) break;
   }
   if (gave_up) atomicAdd(hdr + 1, 1u);
@@ -934,8 +873,7 @@ __global__ __launch_bounds__(kOpBlock, 4) void k_keyed_onepass(KeyArgs A, PrepAr
     if (P.keep) {
       uint32_t pc = __shfl_up(cur[k].c, 1, kWave), pp = __shfl_up(cur[k].p, 1, kWave);
       uint32_t pr = __shfl_up(cur[k].r, 1, kWave), pa = __shfl_up(cur[k].a, 1, kWave);
-      uint64_t pe = (uint64_t(uint32_t(__shfl_up(uint32_t(cur[k].e >> 32), 1, kWave))) << 32) |
-                    uint32_t(__shfl_up(uint32_t(cur[k].e), 1, kWave));
+      uint64_t pe = shfl_up64(cur[k].e, 1);
       uint32_t p2 = 0;  // lane 0: record i-1 shares its predecessor's position
       if (k == 0) {
         if (lane == 0 && live && i > 0) {
@@ -996,8 +934,8 @@ __global__ __launch_bounds__(kOpBlock, 4) void k_keyed_onepass(KeyArgs A, PrepAr
     if (live)
       key_path_sizes(cur[k].c, cur[k].p, cur[k].r, cur[k].a, cur[k].e, cur[k].cd, A.max_seq_len, uint32_t(A.n_chrom),
                      A.digest != nullptr || A.defer, A.code != nullptr, &ks, &ps);
-    K += wave_sum32(ks);
-    Pt += wave_sum32(ps);
+    K += wave_sum(ks);
+    Pt += wave_sum(ps);
   }
   if (lane == 0) {
     s_tk[wv] = K;
@@ -1120,8 +1058,8 @@ __global__ __launch_bounds__(kBlock) void k_keyed_stats(const uint4* __restrict_
   }
   if (rc && hist) atomicAdd(hist + rk, rc);
   if (ctr) {
-    const uint64_t t_rec = wave_sum64(recs);
-    const uint64_t t1 = wave_sum64(e1), t2 = wave_sum64(e2), t3 = wave_sum64(e3);
+    const uint64_t t_rec = wave_sum(recs);
+    const uint64_t t1 = wave_sum(e1), t2 = wave_sum(e2), t3 = wave_sum(e3);
     if (__lane_id() == 0) {
       atomicAdd(&s_c[0], (unsigned long long)t_rec);
       atomicAdd(&s_c[1], (unsigned long long)t1);

@@ -160,14 +160,8 @@ __global__ __launch_bounds__(kBlock) void k_keyset_probe(
     hits += m >= 0;
   }
   if (g_ctr) {
-    for (int d = 32; d > 0; d >>= 1) {
-      hits += __shfl_down(hits, d, kWave);
-      coll += __shfl_down(coll, d, kWave);
-    }
-    if (__lane_id() == 0) {
-      if (hits) atomicAdd(&g_ctr[AVDB_CTR_EXISTING], (unsigned long long)hits);
-      if (coll) atomicAdd(&g_ctr[AVDB_CTR_HASH_COLLISIONS], (unsigned long long)coll);
-    }
+    wave_add(&g_ctr[AVDB_CTR_EXISTING], hits);
+    wave_add(&g_ctr[AVDB_CTR_HASH_COLLISIONS], coll);
   }
 }
 
@@ -217,14 +211,8 @@ __global__ __launch_bounds__(kBlock) void k_keyset_probe_text(
     hits += m >= 0;
   }
   if (g_ctr) {
-    for (int d = 32; d > 0; d >>= 1) {
-      hits += __shfl_down(hits, d, kWave);
-      coll += __shfl_down(coll, d, kWave);
-    }
-    if (__lane_id() == 0) {
-      if (hits) atomicAdd(&g_ctr[AVDB_CTR_EXISTING], (unsigned long long)hits);
-      if (coll) atomicAdd(&g_ctr[AVDB_CTR_HASH_COLLISIONS], (unsigned long long)coll);
-    }
+    wave_add(&g_ctr[AVDB_CTR_EXISTING], hits);
+    wave_add(&g_ctr[AVDB_CTR_HASH_COLLISIONS], coll);
   }
 }
 

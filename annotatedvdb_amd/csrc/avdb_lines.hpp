@@ -80,13 +80,6 @@ __device__ __forceinline__ void for_each_line(const uint8_t* __restrict__ text, 
   }
 }
 
-// v summed over the wave, one atomic per wave
-__device__ __forceinline__ void wave_add(unsigned long long* dst, uint64_t v) {
-  for (int d = 32; d > 0; d >>= 1)
-    v += (uint64_t(uint32_t(__shfl_down(uint32_t(v >> 32), d, kWave))) << 32) | uint32_t(__shfl_down(uint32_t(v), d, kWave));
-  if (__lane_id() == 0 && v) atomicAdd(dst, (unsigned long long)v);
-}
-
 inline size_t pad256(size_t x) { return (x + 255) & ~size_t(255); }
 
 // a table's workspace: count workspace | line starts | marks / row numbers | from next: its own, the scan's temp too

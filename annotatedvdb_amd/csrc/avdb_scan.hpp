@@ -4,6 +4,7 @@
 // rank's line bytes).  Reduce-then-scan over 1,024-element tiles in three short
 // launches — tile sums, one workgroup scanning the tile sums, then each tile
 // scanned again with its base — no look-back across workgroups and no library.
+// The workgroup scan inside each launch is block_excl (avdb_wave.hpp).
 // Two arrays of the same length (K0's record and heap counts, K5's COPY and
 // .mapping sizes) are scanned by the same three launches (exclusive_u64_pair).
 // Traffic is 2 reads + 1 write of each array (8.4 M u64: ~0.2 GB).
@@ -32,35 +33,6 @@ struct Arrays {
   const T* in[NA];
   uint64_t* out[NA];  // (may alias in)
 };
-
-__device__ __forceinline__ uint64_t shfl_up64(uint64_t v, int d) {
-  return (uint64_t(uint32_t(__shfl_up(uint32_t(v >> 32), d, kWave))) << 32) | uint32_t(__shfl_up(uint32_t(v), d, kWave));
-}
-
-// exclusive scan of one u64 per thread over the NT threads of the workgroup;
-// *total = sum.  s_w holds NT / kWave words.
-template <uint32_t NT>
-__device__ __forceinline__ uint64_t block_excl(uint64_t v, uint64_t* s_w, uint64_t* total) {
-  const uint32_t lane = __lane_id(), wv = threadIdx.x / kWave;
-  uint64_t x = v;
-#pragma unroll
-  for (int d = 1; d < kWave; d <<= 1) {
-    const uint64_t u = shfl_up64(x, d);
-    if (lane >= uint32_t(d)) x += u;
-  }
-  if (lane == kWave - 1) s_w[wv] = x;
-  __syncthreads();
-  uint64_t base = 0, tot = 0;
-#pragma unroll
-  for (uint32_t w = 0; w < NT / kWave; ++w) {
-    const uint64_t t = s_w[w];
-    if (w < wv) base += t;
-    tot += t;
-  }
-  __syncthreads();
-  *total = tot;
-  return base + x - v;
-}
 
 template <class T>
 __device__ __forceinline__ void load_run(const T* in, size_t n, size_t i0, uint64_t (&v)[kPer]) {

@@ -41,26 +41,6 @@ struct SmallArgs {
 
 constexpr int kSmallBlock = 256;
 
-__device__ __forceinline__ uint32_t block_excl_scan(uint32_t v, uint32_t* s_tmp, uint32_t* total) {
-  const int lane = __lane_id(), wv = threadIdx.x >> 6;
-  uint32_t x = v;
-#pragma unroll
-  for (int d = 1; d < kWave; d <<= 1) {
-    const uint32_t u = __shfl_up(x, d, kWave);
-    if (lane >= d) x += u;
-  }
-  if (lane == kWave - 1) s_tmp[wv] = x;
-  __syncthreads();
-  uint32_t base = 0, tot = 0;
-  for (int w = 0; w < kSmallBlock / kWave; ++w) {
-    if (w < wv) base += s_tmp[w];
-    tot += s_tmp[w];
-  }
-  __syncthreads();
-  *total = tot;
-  return base + x - v;
-}
-
 __global__ __launch_bounds__(kSmallBlock) void k_small_prep(SmallArgs A) {
   __shared__ uint32_t s_tmp[kSmallBlock / kWave];
   __shared__ uint32_t s_len[AVDB_MAX_CHROM];
@@ -138,7 +118,7 @@ __global__ __launch_bounds__(kSmallBlock) void k_small_prep(SmallArgs A) {
       if (sidx == 2) emit = emit && dst == 0;
       const uint32_t len = emit ? render(sidx, Out<false>(nullptr, 0)).size() : 0u;
       uint32_t tot;
-      const uint32_t at = run[sidx] + block_excl_scan(len, s_tmp, &tot);
+      const uint32_t at = run[sidx] + block_excl<kSmallBlock>(len, s_tmp, &tot);
       uint32_t* offs = A.off_out + size_t(sidx) * (A.n + 1);
       if (live) offs[i] = at;
       if (run[sidx] + tot > A.cap[sidx]) over[sidx] = true;

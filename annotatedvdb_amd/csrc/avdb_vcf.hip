@@ -199,14 +199,13 @@ __global__ __launch_bounds__(kBlock) void k_vcf_count(const uint8_t* __restrict_
       for (int u = 0; u < kNlUnroll; ++u) cw += uint32_t(__popcll(m[u].m0) + __popcll(m[u].m1));
     }
     if (win_cnt) {
-      uint32_t x = cw;
-      for (int d = 32; d > 0; d >>= 1) x += __shfl_xor(x, d, kWave);
+      const uint32_t x = wave_sum(cw);
       if (__lane_id() == 0 && wk < wps) win_cnt[gw * wps + wk] = x;
     }
     c += cw;
     if (!win_cnt) break;
   }
-  for (int d = 32; d > 0; d >>= 1) c += __shfl_xor(c, d, kWave);
+  c = wave_sum(c);
   if (__lane_id() == 0) wave_cnt[gw] = c;
 }
 
@@ -214,21 +213,13 @@ __global__ __launch_bounds__(kBlock) void k_vcf_count(const uint8_t* __restrict_
 __global__ __launch_bounds__(kVcfGrid) void k_vcf_scan_blocks(const uint32_t* __restrict__ wave_cnt,
                                                               unsigned long long* __restrict__ blk_off,
                                                               unsigned long long* __restrict__ total) {
-  __shared__ unsigned long long s[kVcfGrid];
+  __shared__ uint64_t s_w[kVcfGrid / kWave];
   const int t = threadIdx.x;
-  unsigned long long v = 0;
+  uint64_t v = 0, tot;
 #pragma unroll
   for (int w = 0; w < kVcfWaves; ++w) v += wave_cnt[t * kVcfWaves + w];
-  s[t] = v;
-  __syncthreads();
-  for (int d = 1; d < kVcfGrid; d <<= 1) {
-    const unsigned long long x = t >= d ? s[t - d] : 0ull;
-    __syncthreads();
-    s[t] += x;
-    __syncthreads();
-  }
-  blk_off[t] = s[t] - v;
-  if (t == kVcfGrid - 1 && total) *total = s[t];
+  blk_off[t] = block_excl<kVcfGrid>(v, s_w, &tot);
+  if (t == kVcfGrid - 1 && total) *total = tot;
 }
 
 // popcount of `m` over the lanes below this one
@@ -497,29 +488,6 @@ __device__ __forceinline__ uint32_t rs_cand_bits8(uint64_t x, uint64_t nx) {
   return uint32_t((((m & kHiBits) >> 7) * 0x0102040810204080ull) >> 56);
 }
 
-// exclusive block scan of one u32 per thread (kBlock threads); *total = sum
-__device__ __forceinline__ uint32_t block_excl32(uint32_t v, uint32_t* s_w, uint32_t* total) {
-  const uint32_t lane = __lane_id(), wv = threadIdx.x / kWave;
-  uint32_t x = v;
-#pragma unroll
-  for (int d = 1; d < kWave; d <<= 1) {
-    const uint32_t u = __shfl_up(x, d, kWave);
-    if (lane >= uint32_t(d)) x += u;
-  }
-  if (lane == kWave - 1) s_w[wv] = x;
-  __syncthreads();
-  uint32_t base = 0, tot = 0;
-#pragma unroll
-  for (uint32_t w = 0; w < kVcfWaves; ++w) {
-    const uint32_t t = s_w[w];
-    if (w < wv) base += t;
-    tot += t;
-  }
-  __syncthreads();
-  *total = tot;
-  return base + x - v;
-}
-
 // (LOCAL) one line's records into its window's record slots and its REF+ALT bytes
 // into the window's heap slots at window-local heap offset h (the rows emit_line
 // writes, without their final offsets)
@@ -644,7 +612,7 @@ __global__ __launch_bounds__(kBlock, AVDB_VCF_PARSE_WAVES) void k_vcf_parse_wind
     }
   }
   uint32_t T;
-  const uint32_t pref = block_excl32(cnt, s_w, &T);
+  const uint32_t pref = block_excl<kBlock>(cnt, s_w, &T);
   const uint32_t first = w0 == 0 ? 1u : 0u;  // line 0 starts at byte 0
   T += first;
   if (!T) {  // (uniform; no line starts here)
@@ -1001,50 +969,25 @@ struct LocalTot {
 };
 constexpr uint32_t kTileWins = 256;
 
-__device__ __forceinline__ unsigned long long wave_incl_sum64(unsigned long long x) {
-#pragma unroll
-  for (int d = 1; d < kWave; d <<= 1) {
-    const unsigned long long u = scan::shfl_up64(x, d);
-    if (__lane_id() >= uint32_t(d)) x += u;
-  }
-  return x;
-}
-
 __global__ __launch_bounds__(kTileWins) void k_vcf_local_tiles(const LocalWin* __restrict__ win, size_t nw,
                                                                ulonglong2* __restrict__ base_lr,
                                                                unsigned long long* __restrict__ base_h,
                                                                LocalTot* __restrict__ tile_tot) {
-  __shared__ uint32_t s_a[kTileWins / kWave], s_b[kTileWins / kWave];
-  __shared__ unsigned long long s_c[kTileWins / kWave];
-  const uint32_t tid = threadIdx.x, lane = __lane_id(), wv = tid / kWave;
-  const size_t w = size_t(blockIdx.x) * kTileWins + tid;
+  // (lines, records) as a u32 pair and the heap bytes as a u64: the LDS of the
+  // hand-written form, one more barrier pair than a u64 triple
+  __shared__ uint32_t s_lr[2][kTileWins / kWave];
+  __shared__ uint64_t s_h[kTileWins / kWave];
+  const size_t w = size_t(blockIdx.x) * kTileWins + threadIdx.x;
   const LocalWin v = w < nw ? win[w] : LocalWin{0, 0, 0};
-  const uint32_t xa = wave_incl_sum(v.lines), xb = wave_incl_sum(v.recs);
-  const unsigned long long xc = wave_incl_sum64(v.heap);
-  if (lane == kWave - 1) {
-    s_a[wv] = xa;
-    s_b[wv] = xb;
-    s_c[wv] = xc;
-  }
-  __syncthreads();
-  uint32_t pa = 0, pb = 0, ta = 0, tb = 0;
-  unsigned long long pc = 0, tc = 0;
-#pragma unroll
-  for (uint32_t q = 0; q < kTileWins / kWave; ++q) {
-    if (q < wv) {
-      pa += s_a[q];
-      pb += s_b[q];
-      pc += s_c[q];
-    }
-    ta += s_a[q];
-    tb += s_b[q];
-    tc += s_c[q];
-  }
+  uint32_t lr[2] = {v.lines, v.recs}, tlr[2];
+  uint64_t th;
+  block_excl<kTileWins>(lr, s_lr, tlr);
+  const uint64_t ph = block_excl<kTileWins>(uint64_t(v.heap), s_h, &th);
   if (w < nw) {
-    base_lr[w] = make_ulonglong2(pa + xa - v.lines, pb + xb - v.recs);
-    base_h[w] = pc + xc - v.heap;
+    base_lr[w] = make_ulonglong2(lr[0], lr[1]);
+    base_h[w] = ph;
   }
-  if (tid == 0) tile_tot[blockIdx.x] = LocalTot{ta, tb, tc};
+  if (threadIdx.x == 0) tile_tot[blockIdx.x] = LocalTot{tlr[0], tlr[1], th};
 }
 
 // exclusive scan of the tile totals in place (one workgroup), the grand totals to
@@ -1052,37 +995,18 @@ __global__ __launch_bounds__(kTileWins) void k_vcf_local_tiles(const LocalWin* _
 __global__ __launch_bounds__(kTileWins) void k_vcf_local_top(LocalTot* __restrict__ tile, size_t nt,
                                                              unsigned long long* __restrict__ tot,
                                                              unsigned long long* __restrict__ out) {
-  __shared__ unsigned long long s_a[kTileWins / kWave], s_b[kTileWins / kWave], s_c[kTileWins / kWave];
-  const uint32_t tid = threadIdx.x, lane = __lane_id(), wv = tid / kWave;
+  __shared__ uint64_t s_w[3][kTileWins / kWave];
+  const uint32_t tid = threadIdx.x;
   unsigned long long ra = 0, rb = 0, rc = 0;
   for (size_t c0 = 0; c0 < nt; c0 += kTileWins) {
     const size_t i = c0 + tid;
     const LocalTot v = i < nt ? tile[i] : LocalTot{0, 0, 0};
-    const unsigned long long xa = wave_incl_sum64(v.lines), xb = wave_incl_sum64(v.recs),
-                             xc = wave_incl_sum64(v.heap);
-    if (lane == kWave - 1) {
-      s_a[wv] = xa;
-      s_b[wv] = xb;
-      s_c[wv] = xc;
-    }
-    __syncthreads();
-    unsigned long long pa = 0, pb = 0, pc = 0, ta = 0, tb = 0, tc = 0;
-#pragma unroll
-    for (uint32_t q = 0; q < kTileWins / kWave; ++q) {
-      if (q < wv) {
-        pa += s_a[q];
-        pb += s_b[q];
-        pc += s_c[q];
-      }
-      ta += s_a[q];
-      tb += s_b[q];
-      tc += s_c[q];
-    }
-    if (i < nt) tile[i] = LocalTot{ra + pa + xa - v.lines, rb + pb + xb - v.recs, rc + pc + xc - v.heap};
-    ra += ta;
-    rb += tb;
-    rc += tc;
-    __syncthreads();
+    uint64_t x[3] = {v.lines, v.recs, v.heap}, t[3];
+    block_excl<kTileWins>(x, s_w, t);
+    if (i < nt) tile[i] = LocalTot{ra + x[0], rb + x[1], rc + x[2]};
+    ra += t[0];
+    rb += t[1];
+    rc += t[2];
   }
   if (tid == 0) {
     tot[0] = out[0] = ra;

@@ -234,6 +234,55 @@ def _k8_vs_kernels(engine, N, sp):
     assert list(r2["status"]) == [0, 0, 2, 1]
 
 
+_K8_SCAN_REF = {}
+
+
+def _k8_scan_ref(engine):
+    """257 records and, from the batch kernels (K2 + K7 + K5a), the offsets and bytes
+    of their three texts in K8's order (path, key, display); computed once."""
+    if not _K8_SCAN_REF:
+        from annotatedvdb_amd import synth
+        from annotatedvdb_amd.engine import pack_records
+        h = host(synth.alleles(257, seed=87, long_frac=0.04))
+        refs = [h["heap"][o:o + r].tobytes() for o, r in zip(h["allele_off"], h["ref_len"])]
+        alts = [h["heap"][o + r:o + r + a].tobytes() for o, r, a in zip(h["allele_off"], h["ref_len"], h["alt_len"])]
+        recs = ([int(c) for c in h["chrom"]], [int(p) for p in h["pos"]], refs, alts, [int(x) for x in h["ext_id"]])
+        db = pack_records(*recs).to("cuda")
+        end, code, _, _ = engine.record_prep(db, want_lcp=False)
+        kt = engine.primary_keys(db, code=code)
+        text, off, _ = engine.display_attributes(db, end)
+        _K8_SCAN_REF["recs"] = recs
+        _K8_SCAN_REF["texts"] = [(kt.path_off[:258].cpu().numpy(), kt.paths.cpu().numpy().tobytes()),
+                                 (kt.key_off[:258].cpu().numpy(), kt.keys.cpu().numpy().tobytes()),
+                                 (off[:258].cpu().numpy(), text.cpu().numpy().tobytes())]
+    return _K8_SCAN_REF["recs"], _K8_SCAN_REF["texts"]
+
+
+@pytest.mark.parametrize("n", [1, 63, 64, 65, 255, 256, 257])
+def test_k8_text_offsets_equal_batch_kernels(engine, n):
+    """K8's workgroup scan of the text lengths at one record, around one wave and
+    around one workgroup (the second trip carries the running totals): the offsets
+    and bytes of all three texts equal those the batch kernels give the same records."""
+    from annotatedvdb_amd import _native as N
+    recs, texts = _k8_scan_ref(engine)
+    chrom, pos, refs, alts, ext = (x[:n] for x in recs)
+    sp = engine.small()
+    old_mode = sp.mode
+    sp.mode = "gpu"
+    try:
+        res = sp.run(chrom, pos, refs=refs, alts=alts, ext=ext, want=N.SMALL_PATH | N.SMALL_KEY | N.SMALL_DISPLAY)
+        assert res is not None and sp.last_path == "gpu"
+    finally:
+        sp.mode = old_mode
+    _, _, s_out, in_bytes = sp._layout(n, 2)
+    r = s_out.unpack_from(sp._mv, in_bytes)
+    for k, (off, text) in enumerate(texts):
+        got = np.array(r[5 * n + k * (n + 1): 5 * n + (k + 1) * (n + 1)], dtype=np.int64)
+        assert np.array_equal(got, off[: n + 1]), k
+        assert int(off[n]) > 0 or n == 1
+        assert bytes(sp._mv[sp._text0[k]: sp._text0[k] + int(off[n])]) == text[: int(off[n])], k
+
+
 @pytest.mark.parametrize("onepass", [False, True])
 def test_k7_reused_buffers_flag_overflow(engine, onepass):
     """A KeyText reused for a batch whose keys and paths are longer: the texts
@@ -391,14 +440,18 @@ def test_keyed_handoffs_not_taken_after_realloc_or_inplace_edit(engine):
     del ref2
 
 
-def test_k7_block_scan_launch_equals_raw_block_sums(engine):
+# one scan block of 64-record groups exactly; a second block of one group of one
+# record; a second block that ends one record into a group's last wave; four blocks
+@pytest.mark.parametrize("n", [4096 * 64, 4096 * 64 + 1, 4096 * 64 * 2 - 63, 3 * 4096 * 64 + 77])
+def test_k7_block_scan_launch_equals_raw_block_sums(engine, n):
     """Past ctx->k7_raw_blocks blocks of 4,096 groups K7 scans the block totals in
     a launch of its own; below, the write pass sums them.  Both give the same
-    offsets and text (forced here with AVDB_K7_RAW_BLOCKS=0 on a second context)."""
+    offsets and text (forced here with AVDB_K7_RAW_BLOCKS=0 on a second context),
+    and the offsets of the two-call form's size pass (the device-wide scan of
+    avdb_scan.hpp over per-record sizes instead of the group and block scans)."""
     import os
     from annotatedvdb_amd import synth
     from annotatedvdb_amd.engine import Engine
-    n = 3 * 4096 * 64 + 77  # four blocks of 64-record groups
     b = synth.alleles(n, seed=5, long_frac=0.0, device="cuda")
     _, code, _, _ = engine.record_prep(b, want_lcp=False)
     raw = engine.primary_keys(b, code=code)
@@ -413,6 +466,10 @@ def test_k7_block_scan_launch_equals_raw_block_sums(engine):
     assert torch.equal(raw.state[:n], scanned.state[:n])
     kn, pn = int(raw.key_off[n]), int(raw.path_off[n])
     assert torch.equal(raw.keys[:kn], scanned.keys[:kn]) and torch.equal(raw.paths[:pn], scanned.paths[:pn])
+    two = engine.primary_keys(b, code=code, onepass=False)
+    for one in (raw, scanned):
+        assert torch.equal(one.key_off[: n + 1], two.key_off[: n + 1])
+        assert torch.equal(one.path_off[: n + 1], two.path_off[: n + 1])
 
 
 @pytest.mark.parametrize("n,long_frac", [((4 << 20) + 4099, 0.03), (1100000, 0.02), (4097, 0.5), (130, 1.0), (5, 0.4),

@@ -283,6 +283,84 @@ def test_k3_grouped_xyx_runs(engine):
 
 
 # ---------------------------------------------------------------------------
+# K3 mark: the wave-aggregated append of suspects (wave_append, avdb_wave.hpp), in
+# k_dedup_mark4 and in the keyed K2
+# ---------------------------------------------------------------------------
+def _distinct(n):
+    return [(21, 1000 + i, b"A", b"C", 0) for i in range(n)]
+
+
+def _share(recs, first, last, alts):
+    """Records first .. last at record first's position, their ALT from `alts`."""
+    for k, i in enumerate(range(first, last + 1)):
+        recs[i] = (21, recs[first][1], b"A", alts[k:k + 1], 0)
+    return recs
+
+
+@functools.lru_cache(maxsize=None)
+def _append_cases():
+    """name -> (records, suspects): the records that share their predecessor's
+    position, all of them listed by both mark forms (each repeats lengths and id)."""
+    return {
+        # four suspects in every lane of four waves and a three-record scalar tail
+        "every-lane": (tuple([(21, 500, b"A", b"C", 0)] * 1027), 1026),
+        # lane 63 of the first wave alone (it also issues the wave's atomic)
+        "lane-63": (tuple(_share(_distinct(1027), 251, 255, b"CCGGC")), 4),
+        "lane-0": (tuple(_share(_distinct(1027), 0, 1, b"CC")), 1),
+        # the second wave's lane 0, its predecessor the first wave's last record
+        "next-wave-lane-0": (tuple(_share(_distinct(1027), 255, 256, b"CC")), 1),
+        "none": (tuple(_distinct(4096)), 0),
+    }
+
+
+def _oracle_keep(b):
+    import oracle
+    h = {f: getattr(b, f).cpu().numpy() for f in FIELDS}
+    keep = np.empty(b.n, dtype=np.uint8)
+    d = oracle.c_oracle().avdb_oracle_dedup_grouped(
+        h["chrom"].ctypes.data, h["pos"].ctypes.data, h["allele_off"].ctypes.data, h["ref_len"].ctypes.data,
+        h["alt_len"].ctypes.data, h["heap"].ctypes.data, h["ext_id"].ctypes.data, b.n, keep.ctypes.data)
+    return keep, int(d)
+
+
+def _list_counts(ws):
+    """The per-workgroup suspect counts at the head of a K3 list workspace that was
+    filled with 0xA5 bytes before the mark ran: the entries the mark wrote."""
+    head = ws[:16384].view(torch.int32).cpu().numpy().view(np.uint32)
+    return head[head != 0xA5A5A5A5]
+
+
+@pytest.mark.parametrize("keyed", [False, True], ids=["mark4", "keyed-k2"])
+@pytest.mark.parametrize("case", ["every-lane", "lane-63", "lane-0", "next-wave-lane-0", "none"])
+def test_k3_mark_wave_append(engine, case, keyed):
+    """Suspects in every lane, in the wave's last lane only, in its first lane only, in
+    the next wave's first lane only, and in no lane (no atomic: every workgroup's list
+    count stays 0): keep and AVDB_CTR_DUPLICATES equal the C oracle's, from pk_dedup's
+    own mark and from the keyed record prep's marks."""
+    N = _N()
+    recs, suspects = _append_cases()[case]
+    n = len(recs)
+    assert sum(1 for x, y in zip(recs, recs[1:]) if x[:2] == y[:2]) == suspects
+    b = _pack(list(recs)).to(engine.device)
+    want, ndup = _oracle_keep(b)
+    assert ndup == int((want == 0).sum())
+    assert ndup == {"every-lane": 1026, "lane-63": 3, "lane-0": 1, "next-wave-lane-0": 1, "none": 0}[case]
+    ws = torch.full((16384 + 4 * (((n + 3) & ~3) + (1 << 22)),), 0xA5, dtype=torch.uint8, device=engine.device)
+    if keyed:
+        kt = engine.primary_keys(b, code=engine.record_prep(b, want_lcp=False)[1])
+        engine.record_prep(b, want_lcp=False, keys=kt, dedup_workspace=ws)
+        assert "marks" in engine._pending
+    ctr = engine.new_counters()
+    keep = engine.pk_dedup(b, grouped=True, counters=ctr, workspace=ws)
+    assert "marks" not in engine._pending
+    counts = _list_counts(ws)
+    assert counts.size >= 1 and int(counts.sum()) == suspects, counts[:8].tolist()
+    bad = np.nonzero(keep.cpu().numpy()[:n] != want)[0]
+    assert bad.size == 0, bad[:8].tolist()
+    assert int(ctr[N.CTR_DUPLICATES]) == ndup
+
+
+# ---------------------------------------------------------------------------
 # K3 hash path
 # ---------------------------------------------------------------------------
 def _hash_dedup(engine, recs):

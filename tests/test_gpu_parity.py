@@ -209,7 +209,8 @@ def test_k2_random_vs_c_oracle(engine):
     import oracle
     from annotatedvdb_amd import synth
     b = synth.alleles(1_000_000, seed=21)
-    end, code, status, lcp = engine.record_prep(b)
+    ctr = engine.new_counters()
+    end, code, status, lcp = engine.record_prep(b, counters=ctr)
     h = {k: getattr(b, k).cpu().numpy() for k in ("chrom", "pos", "allele_off", "ref_len", "alt_len", "heap")}
     n = b.n
     re_, rc, rl = (np.empty(n, dtype=np.uint32) for _ in range(3))
@@ -223,6 +224,18 @@ def test_k2_random_vs_c_oracle(engine):
     assert np.array_equal(u32(code), rc)
     assert np.array_equal(status.cpu().numpy(), rs)
     assert np.array_equal(u32(lcp), rl)
+    # AVDB_CTR_RECORDS and the per-status counts, from the 4-records-per-lane form and
+    # (views that start one record in) the one-record-per-lane form
+    c = ctr.cpu().numpy()
+    assert int(c[20]) == n and c[16:20].tolist() == np.bincount(rs, minlength=4).tolist()
+    from annotatedvdb_amd.engine import RecordBatch
+    v = RecordBatch(**{f: (getattr(b, f)[1:] if f != "heap" else b.heap)
+                       for f in ("chrom", "pos", "allele_off", "ref_len", "alt_len", "heap", "ext_id")})
+    ctr = engine.new_counters()
+    _, _, status1, _ = engine.record_prep(v, counters=ctr)
+    assert np.array_equal(status1.cpu().numpy(), rs[1:])
+    c = ctr.cpu().numpy()
+    assert int(c[20]) == n - 1 and c[16:20].tolist() == np.bincount(rs[1:], minlength=4).tolist()
 
 
 # ---------------------------------------------------------------------------

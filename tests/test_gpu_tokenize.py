@@ -206,8 +206,31 @@ def test_k0_window_parse_equals_starts_pass(engine, which):
     assert (vb.heap_off[: n0 + 1].cpu().numpy() == ho0).all()
 
 
+def _local_windows(nbytes):
+    """Parse windows of the count-free path for a text of nbytes (local_layout,
+    avdb_vcf.hip, restated): the text is cut into 4,096 sub-chunks of a multiple of 64
+    bytes, each sub-chunk that holds text into windows of 24 KiB."""
+    per = (-(-nbytes // 4096) + 63) & ~63
+    return -(-nbytes // per) * -(-per // (24 * 1024))
+
+
+def _golden_repeated(engine, nbytes):
+    """nbytes of the golden data lines, repeated on the device (the cut may end in a line)."""
+    g = torch.frombuffer(bytearray(_golden_text()), dtype=torch.uint8).to(engine.device)
+    return g.repeat(-(-nbytes // g.numel()))[:nbytes].contiguous()
+
+
+# Texts of exactly 255 / 256 / 257 / 513 parse windows: one workgroup of
+# k_vcf_local_tiles less one window, full, one window into the second, and three tiles
+# for k_vcf_local_top.  A text under 100 MB has one window per 64-byte-aligned
+# 1/4,096th of it, so these window counts are texts of 64 bytes per window ("win*");
+# the same counts of 24 KiB ("kib*", up to 12.6 MB) are ~4,000 windows in 16 tiles.
+WINDOW_TEXTS = {"win%d" % w: 64 * w for w in (255, 256, 257, 513)}
+WINDOW_TEXTS.update({"kib%d" % w: 24 * 1024 * w for w in (255, 256, 257, 513)})
+
+
 @pytest.mark.parametrize("which", ["golden", "dbsnp", "long", "big", "short", "edges", "empty", "no_final_nl",
-                                   "blank", "huge_heap"])
+                                   "blank", "huge_heap"] + sorted(WINDOW_TEXTS))
 @pytest.mark.parametrize("count_free", [True, False])
 def test_k0_records_without_line_table(engine, which, count_free):
     """vcf_tokenize(want_lines=False) — no public line table: the count-free path
@@ -216,11 +239,18 @@ def test_k0_records_without_line_table(engine, which, count_free):
     parse -> avdb_vcf_emit_ws from 32-byte records — gives the same record SoA,
     allele heap, offsets and back-references as the tokenizer with the table.
     "short": 17-byte lines; "edges": blank lines, CRLF, lines of one field, a final
-    line without '\n'; "blank": 8 M empty lines around dbSNP lines — more lines in a
+    line without '\n'; WINDOW_TEXTS: window counts at the edges of the
+    two-level scan of the window totals; "blank": 8 M empty lines around dbSNP lines — more lines in a
     parse window than its 1,024 slots, so the count-free call falls back to the
     counted path; "huge_heap": a line whose records hold 9 MB of heap (> 2^23 bytes,
     past the slot's in-window offsets), so the count-free call falls back too."""
-    if which == "short":
+    if which in WINDOW_TEXTS:
+        text = _golden_repeated(engine, WINDOW_TEXTS[which])
+        if which.startswith("win"):
+            assert _local_windows(text.numel()) == int(which[3:])
+        else:
+            assert 3 * 256 < _local_windows(text.numel()) <= 4096
+    elif which == "short":
         text = b"".join(b"%d\t%d\t.\tA\tG\t.\t.\t.\n" % (1 + i % 9, 10 + i % 90) for i in range(300000))
     elif which == "golden":
         text = _golden_text()
@@ -251,6 +281,8 @@ def test_k0_records_without_line_table(engine, which, count_free):
     b = engine.vcf_tokenize(text, want_lines=False, count_free=count_free)
     assert engine.last_vcf_path == ("counted" if which in ("blank", "huge_heap") or not count_free else "local")
     assert b.lines is None and a.n_lines == b.n_lines and a.records.n == b.records.n
+    if which in WINDOW_TEXTS:
+        assert a.n_lines >= WINDOW_TEXTS[which] // 400 and a.records.n >= a.n_lines // 2
     assert torch.equal(a.rec_off, b.rec_off) and torch.equal(a.heap_off, b.heap_off)
     for f in ("chrom", "pos", "allele_off", "ref_len", "alt_len", "ext_id"):
         assert torch.equal(getattr(a.records, f), getattr(b.records, f)), f
