@@ -16,7 +16,8 @@ import os
 import threading
 from typing import Optional
 
-import torch  # noqa: F401  (loads torch's HIP runtime before ours; see module doc)
+import numpy as np
+import torch  # (loads torch's HIP runtime before ours; see module doc)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "_lib", "libavdb_hip.so")
@@ -317,6 +318,45 @@ def ptr(t) -> int:
     if t is None:
         return None
     return t.data_ptr()
+
+
+_ARRAYS = (torch.Tensor, np.ndarray)
+
+
+def symbol(name: str):
+    """The library's entry ``name``."""
+    return getattr(_lib if _lib is not None else load_library(), name)
+
+
+def call(name: str, *args, check: bool = True) -> int:
+    """The one way from Python into the library (the per-call hot paths aside,
+    DESIGN.md §1): entry ``name`` on ``args`` — a tensor goes as its ``data_ptr()``,
+    a numpy array as its ``.ctypes.data``, None as NULL, anything else (ints,
+    ``ctypes.byref``, structures, bytes) as it is.  The entries read every array as
+    dense, so a strided one raises ``ValueError`` here, before the library is
+    entered.  Returns the entry's code; a negative one raises :class:`NativeError`
+    under the name called (``check=False``: the caller reads the code)."""
+    conv = list(args)
+    for i, a in enumerate(args):
+        if isinstance(a, _ARRAYS):
+            if isinstance(a, torch.Tensor):
+                dense, conv[i] = a.is_contiguous(), a.data_ptr()
+            else:
+                dense, conv[i] = a.flags.c_contiguous, a.ctypes.data
+            if not dense:
+                raise ValueError(f"{name}: argument {i} is a strided {type(a).__name__} "
+                                 "(the library reads dense arrays)")
+    rc = symbol(name)(*conv)
+    if rc < 0 and check:
+        raise NativeError(name, rc, last_error())
+    return rc
+
+
+def size(name: str, *dims) -> int:
+    """A size query (``avdb_*_workspace_size`` and the like): its one ``size_t`` result."""
+    sz = ctypes.c_size_t()
+    call(name, *dims, ctypes.byref(sz))
+    return int(sz.value)
 
 
 def stream_handle(device=None) -> int:

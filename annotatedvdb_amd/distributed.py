@@ -100,8 +100,7 @@ class RcclExchange:
         self.world = world
         comm = ctypes.c_void_p()
         buf = ctypes.create_string_buffer(bytes(unique_id), N.RCCL_ID_BYTES)
-        N.check("avdb_rccl_comm_init", engine.lib.avdb_rccl_comm_init(engine.ctx, world, rank, buf,
-                                                                     ctypes.byref(comm)))
+        N.call("avdb_rccl_comm_init", engine.ctx, world, rank, buf, ctypes.byref(comm))
         self.comm = comm
 
     @staticmethod
@@ -109,34 +108,28 @@ class RcclExchange:
         import ctypes
         from . import _native as N
         buf = ctypes.create_string_buffer(N.RCCL_ID_BYTES)
-        N.check("avdb_rccl_unique_id", N.load_library().avdb_rccl_unique_id(buf))
+        N.call("avdb_rccl_unique_id", buf)
         return buf.raw
 
     def allgather(self, hist: torch.Tensor, counters: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
-        import ctypes
         N, e = self._N, self.engine
-        # avdb_hist_allgather reads u32 bins and u64 counters from raw device pointers
+        # avdb_hist_allgather reads u32 bins and u64 counters from raw device pointers (dense: N.call checks)
         if hist.dtype not in (torch.int32, torch.uint32) or counters.dtype not in (torch.int64, torch.uint64):
             raise ValueError("hist must be int32/uint32 and counters int64/uint64 (got %s, %s)"
                              % (hist.dtype, counters.dtype))
-        if not (hist.is_contiguous() and counters.is_contiguous()):
-            raise ValueError("hist and counters must be contiguous")
         if hist.device != e.device or counters.device != e.device:
             raise ValueError("hist and counters must be on the engine's device %s" % e.device)
         nb, nc = hist.numel(), counters.numel()
-        sz = ctypes.c_size_t()
-        N.check("avdb_hist_allgather_workspace_size",
-                e.lib.avdb_hist_allgather_workspace_size(self.world, nb, nc, ctypes.byref(sz)))
-        ws = torch.empty(int(sz.value), dtype=torch.uint8, device=hist.device)
+        ws = torch.empty(N.size("avdb_hist_allgather_workspace_size", self.world, nb, nc), dtype=torch.uint8,
+                         device=hist.device)
         node_h, node_c = torch.empty_like(hist), torch.empty_like(counters)
-        N.check("avdb_hist_allgather", e.lib.avdb_hist_allgather(
-            e.ctx, self.comm, N.ptr(hist), nb, N.ptr(counters), nc, N.ptr(node_h), N.ptr(node_c), N.ptr(ws),
-            ws.numel(), e._stream()))
+        N.call("avdb_hist_allgather", e.ctx, self.comm, hist, nb, counters, nc, node_h, node_c, ws, ws.numel(),
+               e._stream())
         return node_h, node_c
 
     def close(self):
         if self.comm:
-            self._N.check("avdb_rccl_comm_destroy", self.engine.lib.avdb_rccl_comm_destroy(self.comm))
+            self._N.call("avdb_rccl_comm_destroy", self.comm)
             self.comm = None
 
 

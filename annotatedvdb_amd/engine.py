@@ -66,6 +66,10 @@ class RecordBatch:
     def has_alleles(self) -> bool:
         return self.heap is not None
 
+    def soa(self) -> tuple:
+        """The seven record arguments most batch entries begin with (``include/avdb.h``)."""
+        return (self.chrom, self.pos, self.allele_off, self.ref_len, self.alt_len, self.heap, self.heap.numel())
+
 
 @dataclass
 class CaddColumns:
@@ -184,6 +188,13 @@ def pack_records(chrom_codes: Sequence[int], pos: Sequence[int], refs: Sequence[
         heap=torch.from_numpy(heap_np.copy()),
         ext_id=torch.from_numpy(ext),
     )
+
+
+def dedup_list_bytes(n: int, slack: int = 0) -> int:
+    """Bytes of K3's list workspace for ``n`` records (``kDedupListHead`` in
+    ``csrc/avdb_internal.hpp``: a 16 KiB head, then one u32 entry per record, rounded up
+    to four) with room for ``slack`` more entries."""
+    return 16384 + 4 * (((n + 3) & ~3) + slack)
 
 
 def as_u32(t: torch.Tensor) -> np.ndarray:
@@ -385,7 +396,7 @@ class SmallPrep:
             self._host_arena = np.zeros(total + 64, dtype=np.uint8)
             return (self._host_arena.ctypes.data + 63) & ~63
         p = ctypes.c_void_p()
-        N.check("avdb_host_alloc", self.eng.lib.avdb_host_alloc(total, ctypes.byref(p)))
+        N.call("avdb_host_alloc", total, ctypes.byref(p))
         return p.value
 
     def close(self):
@@ -558,8 +569,7 @@ class ChromMap:
         blob = np.frombuffer(b"".join(keys) or b"\0", dtype=np.uint8)
         cd = np.asarray(codes or [0], dtype=np.uint8)
         h = ctypes.c_void_p()
-        N.check("avdb_chrom_map_create", engine.lib.avdb_chrom_map_create(
-            engine.ctx, blob.ctypes.data, off.ctypes.data, len(keys), cd.ctypes.data, ctypes.byref(h)))
+        N.call("avdb_chrom_map_create", engine.ctx, blob, off, len(keys), cd, ctypes.byref(h))
         self.handle = h.value
         self.n_keys = len(keys)
 
@@ -643,11 +653,11 @@ class Engine:
         self.lengths = list(lengths) if lengths is not None else length_table(assembly)
         arr = (ctypes.c_uint32 * len(self.lengths))(*self.lengths)
         h = ctypes.c_void_p()
-        N.check("avdb_ctx_create", self.lib.avdb_ctx_create(-1 if self.host_only else self.device.index, arr,
-                                                            len(self.lengths), ctypes.byref(h)))
+        N.call("avdb_ctx_create", -1 if self.host_only else self.device.index, arr, len(self.lengths),
+               ctypes.byref(h))
         self._ctx = h
         nb = ctypes.c_uint32()
-        self.lib.avdb_l8_bin_count(self._ctx, ctypes.byref(nb))
+        self._call("avdb_l8_bin_count", ctypes.byref(nb))
         self.n_l8 = int(nb.value)
         # what the last keyed K2 left for its consumers, each entry tied (by _stamp)
         # to the exact tensors it was computed from and taken by the one call it
@@ -691,6 +701,14 @@ class Engine:
                                       "this batch entry is a gfx950 kernel and needs a GPU")
         return N.stream_handle(self.device)
 
+    def _call(self, name: str, *args) -> int:
+        """``N.call`` of a context entry."""
+        return N.call(name, self.ctx, *args)
+
+    def _launch(self, name: str, *args) -> int:
+        """``N.call`` of a kernel entry: on the context, into the current stream."""
+        return N.call(name, self.ctx, *args, self._stream())
+
     def small(self) -> SmallPrep:
         """The engine's K8 arena (created on first use)."""
         sp = getattr(self, "_small", None)
@@ -722,8 +740,7 @@ class Engine:
         if len(digests) != len(self.lengths) or any(len(d) != N.DIGEST_CHARS for d in digests):
             raise ValueError("need one 32-character refget digest per chromosome")
         blob = "".join(digests).encode("ascii")
-        N.check("avdb_ctx_set_sequence_digests",
-                self.lib.avdb_ctx_set_sequence_digests(self.ctx, blob, len(digests)))
+        self._call("avdb_ctx_set_sequence_digests", blob, len(digests))
 
     # -- buffers -----------------------------------------------------------
     def empty(self, n, dtype):
@@ -746,9 +763,19 @@ class Engine:
             t.fill_(self.poison)
         return t
 
+    def workspace(self, nbytes: int, given: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The caller's workspace when it holds ``nbytes``, else a fresh one."""
+        return given if given is not None and given.numel() >= nbytes else self.empty(nbytes, torch.uint8)
+
+    def _batch(self, b: RecordBatch) -> RecordBatch:
+        """``b`` on the engine's device, its allele arrays checked."""
+        b = b if b.device == self.device else b.to(self.device)
+        self._check_alleles(b)
+        return b
+
     def set_option(self, option: int, value: int):
         """``avdb_ctx_set_option`` (launch shape only: ``N.OPT_K4_GRID``)."""
-        N.check("avdb_ctx_set_option", self.lib.avdb_ctx_set_option(self.ctx, int(option), int(value)))
+        self._call("avdb_ctx_set_option", int(option), int(value))
 
     def new_histogram(self) -> torch.Tensor:
         return torch.zeros(self.n_l8, dtype=torch.int32, device=self.device)
@@ -781,9 +808,7 @@ class Engine:
             status = out_status if out_status is not None else self.empty(n, torch.uint8)
         if hist is not None and hist.numel() != self.n_l8:
             raise ValueError("histogram must have n_l8 bins")
-        N.check("avdb_bin_assign", self.lib.avdb_bin_assign(
-            self.ctx, N.ptr(chrom), N.ptr(start), N.ptr(end), n, N.ptr(code), N.ptr(status),
-            N.ptr(hist), N.ptr(counters), self._stream()))
+        self._launch("avdb_bin_assign", chrom, start, end, n, code, status, hist, counters)
         return code, status
 
     # -- K2 ----------------------------------------------------------------
@@ -803,36 +828,31 @@ class Engine:
         gets) it runs K3's first phase, so that call only resolves the listed runs.
         Either workspace without ``keys`` runs the same K2 without K7's totals (a
         step with no key text, as C5's)."""
-        b = b if b.device == self.device else b.to(self.device)
+        b = self._batch(b)
         n = b.n
-        self._check_alleles(b)
         self._pending.clear()
         end = self.empty(n, torch.int32)
         code = self.empty(n, torch.int32)
         status = self.empty(n, torch.uint8)
         lcp = self.empty(n, torch.int32) if want_lcp else None
-        args = (self.ctx, N.ptr(b.chrom), N.ptr(b.pos), N.ptr(b.allele_off), N.ptr(b.ref_len),
-                N.ptr(b.alt_len), N.ptr(b.heap), b.heap.numel(), n, N.ptr(end), N.ptr(code), N.ptr(status),
-                N.ptr(lcp), N.ptr(hist), N.ptr(counters))
+        args = (*b.soa(), n, end, code, status, lcp, hist, counters)
         if keys is None and digest_workspace is None and dedup_workspace is None:
-            N.check("avdb_record_prep", self.lib.avdb_record_prep(*args, self._stream()))
+            self._launch("avdb_record_prep", *args)
             return end, code, status, lcp
         dws = digest_workspace
         if dws is not None:
-            sz = ctypes.c_size_t()
-            self.lib.avdb_vrs_digest_workspace_size(n, ctypes.byref(sz))
-            if dws.numel() < sz.value:
-                raise ValueError("record_prep: digest_workspace needs %d bytes" % sz.value)
+            need = N.size("avdb_vrs_digest_workspace_size", n)
+            if dws.numel() < need:
+                raise ValueError("record_prep: digest_workspace needs %d bytes" % need)
         ddw = dedup_workspace
         keep = None
         if ddw is not None:
             keep = self.empty(max(4, n), torch.uint8)
         done = ctypes.c_int(0)
-        N.check("avdb_record_prep_keyed", self.lib.avdb_record_prep_keyed(
-            *args, N.ptr(b.ext_id), int(max_seq_len), 1 if key_digest else 0, 1 if key_paths else 0,
-            N.ptr(keys.ws) if keys is not None else None, keys.ws.numel() if keys is not None else 0,
-            N.ptr(dws), dws.numel() if dws is not None else 0,
-            N.ptr(ddw), ddw.numel() if ddw is not None else 0, N.ptr(keep), ctypes.byref(done), self._stream()))
+        self._launch("avdb_record_prep_keyed", *args, b.ext_id, int(max_seq_len), 1 if key_digest else 0,
+                     1 if key_paths else 0, keys.ws if keys is not None else None,
+                     keys.ws.numel() if keys is not None else 0, dws, dws.numel() if dws is not None else 0,
+                     ddw, ddw.numel() if ddw is not None else 0, keep, ctypes.byref(done))
         # (tied to these exact tensors: another batch, a reallocated one or an
         # in-place edit recomputes)
         if done.value & N.KEYED_TOTALS:
@@ -857,30 +877,24 @@ class Engine:
         runs; the next ``pk_dedup(b, workspace=...)`` resolves them), else ``keep`` is
         None.  ``workspace``: ``avdb_keyed_prep_workspace_size`` bytes (allocated
         when None)."""
-        b = b if b.device == self.device else b.to(self.device)
+        b = self._batch(b)
         n = b.n
-        self._check_alleles(b)
         self._pending.clear()
         if kt.key_off.numel() < n + 1 or kt.state.numel() < max(1, n) or kt.keys is None or kt.off32:
             raise ValueError("keyed_prep: the KeyText holds fewer records (or narrow offsets)")
-        sz = ctypes.c_size_t()
-        self.lib.avdb_keyed_prep_workspace_size(n, ctypes.byref(sz))
-        ws = workspace if workspace is not None and workspace.numel() >= sz.value else \
-            self.empty(int(sz.value), torch.uint8)
+        ws = self.workspace(N.size("avdb_keyed_prep_workspace_size", n), workspace)
         end = self.empty(n, torch.int32)
         code = self.empty(n, torch.int32)
         status = self.empty(n, torch.uint8)
         dws, ddw = digest_workspace, dedup_workspace
         keep = self.empty(max(4, n), torch.uint8) if ddw is not None else None
         done = ctypes.c_int(0)
-        N.check("avdb_keyed_prep", self.lib.avdb_keyed_prep(
-            self.ctx, N.ptr(b.chrom), N.ptr(b.pos), N.ptr(b.allele_off), N.ptr(b.ref_len), N.ptr(b.alt_len),
-            N.ptr(b.heap), b.heap.numel(), N.ptr(b.ext_id), n, int(max_seq_len), N.ptr(end), N.ptr(code),
-            N.ptr(status), N.ptr(hist), N.ptr(counters), N.ptr(ws), ws.numel(), N.ptr(dws),
-            dws.numel() if dws is not None else 0, N.ptr(ddw), ddw.numel() if ddw is not None else 0, N.ptr(keep),
-            N.ptr(kt.key_off), N.ptr(kt.path_off) if kt.paths is not None else None, N.ptr(kt.keys), kt.keys.numel(),
-            N.ptr(kt.paths), kt.paths.numel() if kt.paths is not None else 0, N.ptr(kt.state),
-            N.KEYS_DIGEST_DEFERRED if defer_digest else 0, ctypes.byref(done), self._stream()))
+        self._launch("avdb_keyed_prep", *b.soa(), b.ext_id, n, int(max_seq_len), end, code, status, hist, counters,
+                     ws, ws.numel(), dws, dws.numel() if dws is not None else 0, ddw,
+                     ddw.numel() if ddw is not None else 0, keep, kt.key_off,
+                     kt.path_off if kt.paths is not None else None, kt.keys, kt.keys.numel(), kt.paths,
+                     kt.paths.numel() if kt.paths is not None else 0, kt.state,
+                     N.KEYS_DIGEST_DEFERRED if defer_digest else 0, ctypes.byref(done))
         self.last_keyed_ws = ws
         if done.value & N.KEYED_LONG_CODES:
             self._pending["codes"] = (_stamp(dws, b.ref_len, b.alt_len), n, int(max_seq_len))
@@ -892,45 +906,29 @@ class Engine:
         """Look-back polls that gave up in the last ``keyed_prep`` on ``workspace``
         (a host sync; 0 expected)."""
         v = ctypes.c_uint32()
-        N.check("avdb_keyed_prep_lookback_errors",
-                self.lib.avdb_keyed_prep_lookback_errors(self.ctx, N.ptr(workspace), ctypes.byref(v)))
+        self._call("avdb_keyed_prep_lookback_errors", workspace, ctypes.byref(v))
         return int(v.value)
 
     # -- K3 ----------------------------------------------------------------
     def pk_dedup(self, b: RecordBatch, *, grouped: bool = True,
                  counters: Optional[torch.Tensor] = None,
                  workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
-        b = b if b.device == self.device else b.to(self.device)
+        b = self._batch(b)
         n = b.n
-        self._check_alleles(b)
         marks = self._pending.pop("marks", None)
         if (grouped and workspace is not None and marks is not None and marks[1] == n
                 and _stamp_ok(marks[0], workspace, b.chrom, b.pos)):
             # the keyed K2 already wrote keep = 1 and listed the runs: resolve them
             keep = marks[2]
             flags = N.DEDUP_MARKED | (marks[3] if len(marks) > 3 else 0)
-            N.check("avdb_pk_dedup_ex", self.lib.avdb_pk_dedup_ex(
-                self.ctx, N.ptr(b.chrom), N.ptr(b.pos), N.ptr(b.allele_off), N.ptr(b.ref_len),
-                N.ptr(b.alt_len), N.ptr(b.heap), b.heap.numel(), N.ptr(b.ext_id), n, N.ptr(workspace),
-                workspace.numel(), N.ptr(keep), N.ptr(counters), flags, self._stream()))
+            self._launch("avdb_pk_dedup_ex", *b.soa(), b.ext_id, n, workspace, workspace.numel(), keep, counters,
+                         flags)
             return keep[:n]
         keep = self.empty(n, torch.uint8)
-        ws = None
-        ws_bytes = 0
-        if grouped:  # optional list of same-position records (two-phase run scan)
-            ws_bytes = 16384 + 4 * ((n + 3) & ~3)
-            ws = workspace if workspace is not None and workspace.numel() >= ws_bytes else \
-                self.empty(ws_bytes, torch.uint8)
-        else:
-            sz = ctypes.c_size_t()
-            self.lib.avdb_pk_dedup_workspace_size(n, ctypes.byref(sz))
-            ws_bytes = int(sz.value)
-            ws = workspace if workspace is not None and workspace.numel() >= ws_bytes else \
-                self.empty(ws_bytes, torch.uint8)
-        N.check("avdb_pk_dedup", self.lib.avdb_pk_dedup(
-            self.ctx, N.ptr(b.chrom), N.ptr(b.pos), N.ptr(b.allele_off), N.ptr(b.ref_len),
-            N.ptr(b.alt_len), N.ptr(b.heap), b.heap.numel(), N.ptr(b.ext_id), n, 1 if grouped else 0,
-            N.ptr(ws), ws_bytes, N.ptr(keep), N.ptr(counters), self._stream()))
+        # grouped: the list of same-position records (two-phase run scan)
+        ws_bytes = dedup_list_bytes(n) if grouped else N.size("avdb_pk_dedup_workspace_size", n)
+        ws = self.workspace(ws_bytes, workspace)
+        self._launch("avdb_pk_dedup", *b.soa(), b.ext_id, n, 1 if grouped else 0, ws, ws_bytes, keep, counters)
         return keep
 
     # -- K4 ----------------------------------------------------------------
@@ -943,29 +941,23 @@ class Engine:
         ``keys``: the ``KeyText`` of a deferred ``primary_keys`` / ``keyed_prep``
         on this batch — the digests also go into its pending keys
         (``avdb_vrs_digest_keys``: no :meth:`fill_digests` pass)."""
-        b = b if b.device == self.device else b.to(self.device)
+        b = self._batch(b)
         n = b.n
-        self._check_alleles(b)
         dig = self.empty(max(1, n) * N.DIGEST_CHARS, torch.uint8).view(-1, N.DIGEST_CHARS)[:n]
         is_long = self.empty(n, torch.uint8)
-        sz = ctypes.c_size_t()
-        self.lib.avdb_vrs_digest_workspace_size(n, ctypes.byref(sz))
-        ws = workspace if workspace is not None and workspace.numel() >= sz.value else \
-            self.empty(int(sz.value), torch.uint8)
+        need = N.size("avdb_vrs_digest_workspace_size", n)
+        ws = self.workspace(need, workspace)
         # the keyed K2 classified this batch's records into this workspace
         codes = self._pending.pop("codes", None)
         ready = (codes is not None and codes[1:] == (n, int(max_seq_len))
                  and _stamp_ok(codes[0], ws, b.ref_len, b.alt_len))
-        args = (self.ctx, N.ptr(b.chrom), N.ptr(b.pos), N.ptr(b.allele_off), N.ptr(b.ref_len),
-                N.ptr(b.alt_len), N.ptr(b.heap), b.heap.numel(), n, int(max_seq_len), N.ptr(ws), int(sz.value),
-                N.ptr(dig), N.ptr(is_long), N.DIGEST_CODES_READY if ready else 0)
+        args = (*b.soa(), n, int(max_seq_len), ws, need, dig, is_long, N.DIGEST_CODES_READY if ready else 0)
         if keys is None:
-            N.check("avdb_vrs_digest_ex", self.lib.avdb_vrs_digest_ex(*args, self._stream()))
+            self._launch("avdb_vrs_digest_ex", *args)
         else:
             if keys.off32:
                 raise ValueError("vrs_digest(keys=...): narrow key offsets are not accepted")
-            N.check("avdb_vrs_digest_keys", self.lib.avdb_vrs_digest_keys(
-                *args, N.ptr(keys.key_off), N.ptr(keys.keys), N.ptr(keys.state), self._stream()))
+            self._launch("avdb_vrs_digest_keys", *args, keys.key_off, keys.keys, keys.state)
         return dig, is_long
 
     def sha512t24u(self, blobs: Sequence[bytes]) -> List[str]:
@@ -980,8 +972,7 @@ class Engine:
         d_off = torch.from_numpy(off).to(self.device)
         d_len = torch.from_numpy(lens.astype(np.int32)).to(self.device)
         out = self.empty(n * N.DIGEST_CHARS, torch.uint8)
-        N.check("avdb_sha512t24u", self.lib.avdb_sha512t24u(
-            self.ctx, N.ptr(d_data), N.ptr(d_off), N.ptr(d_len), n, N.ptr(out), self._stream()))
+        self._launch("avdb_sha512t24u", d_data, d_off, d_len, n, out)
         raw = out.cpu().numpy().tobytes()
         return [raw[i * 32:(i + 1) * 32].decode("ascii") for i in range(n)]
 
@@ -1005,25 +996,16 @@ class Engine:
             # (a window overflowed its line slots: the counted path, on the text the
             # count-free attempt already put on the device)
         self.last_vcf_path = "counted"
+        last_nl = None  # (device text: read with the newline count, one host sync, not two)
         if isinstance(text, (bytes, bytearray, memoryview)):
-            host = bytes(text)
-            t = torch.frombuffer(bytearray(host) if host else bytearray(b"\n"), dtype=torch.uint8)
-            if not host:
-                t = t[:0]
-            text_t = t.to(self.device)
-            last_nl = host.endswith(b"\n") if host else True
-        else:
-            text_t = self._dev(text)
-            last_nl = None  # (read with the newline count: one host sync, not two)
+            text = bytes(text)
+            last_nl = text.endswith(b"\n") if text else True
+        text_t = self._as_text(text)
         nb = int(text_t.numel())
-        tp = N.ptr(text_t) if nb else None
-        s = self._stream()
-        csz = ctypes.c_size_t()
-        self.lib.avdb_vcf_count_workspace_size(nb, ctypes.byref(csz))  # (with the parse windows' counts)
-        ws0 = self.empty(int(csz.value), torch.uint8)
+        tp = text_t if nb else None
+        ws0 = self.empty(N.size("avdb_vcf_count_workspace_size", nb), torch.uint8)  # (with the parse windows' counts)
         nl = torch.zeros(2, dtype=torch.int64, device=self.device)  # newlines, last byte
-        N.check("avdb_vcf_count_lines", self.lib.avdb_vcf_count_lines(
-            self.ctx, tp, nb, N.ptr(ws0), ws0.numel(), N.ptr(nl), s))
+        self._launch("avdb_vcf_count_lines", tp, nb, ws0, ws0.numel(), nl)
         if last_nl is None and nb:
             nl[1:2].copy_(text_t[-1:])
         got = nl.cpu()
@@ -1031,20 +1013,28 @@ class Engine:
         if last_nl is None:
             last_nl = nb == 0 or int(got[1]) == 10
         n_lines = n_nl + (0 if (last_nl or nb == 0) else 1)
-        sz = ctypes.c_size_t()
-        self.lib.avdb_vcf_workspace_size(nb, n_lines, ctypes.byref(sz))
-        ws = self.empty(int(sz.value), torch.uint8)
+        ws = self.empty(N.size("avdb_vcf_workspace_size", nb, n_lines), torch.uint8)
         lines = self.empty(max(1, n_lines) * VCF_LINE_DTYPE.itemsize, torch.uint8) if want_lines else None
         rec_off = self.empty(n_lines + 1, torch.int64)
         heap_off = self.empty(n_lines + 1, torch.int64)
-        N.check("avdb_vcf_parse_lines2", self.lib.avdb_vcf_parse_lines2(
-            self.ctx, tp, nb, n_lines, N.ptr(ws0), ws0.numel(), N.ptr(ws), ws.numel(), N.ptr(lines), N.ptr(rec_off),
-            N.ptr(heap_off), ctypes.byref(vcf_opts) if vcf_opts is not None else None, s))
+        self._launch("avdb_vcf_parse_lines2", tp, nb, n_lines, ws0, ws0.numel(), ws, ws.numel(), lines, rec_off,
+                     heap_off, ctypes.byref(vcf_opts) if vcf_opts is not None else None)
         if n_lines:
             tot = torch.stack([rec_off[n_lines], heap_off[n_lines]]).cpu().tolist()
         else:
             tot = [0, 0]
-        n_rec, n_heap = int(tot[0]), int(tot[1])
+        n_rec = int(tot[0])
+        b, rec_line, rec_alt, outs = self._tokenizer_outputs(n_rec, int(tot[1]))
+        if n_rec and want_lines:
+            self._launch("avdb_vcf_emit", tp, nb, n_lines, lines, rec_off, heap_off, *outs)
+        elif n_rec:
+            self._launch("avdb_vcf_emit_ws", tp, nb, n_lines, ws, ws.numel(), rec_off, heap_off, *outs)
+        return VcfBatch(text=text_t, n_lines=n_lines, lines=lines, rec_off=rec_off, heap_off=heap_off,
+                        records=b, rec_line=rec_line, rec_alt=rec_alt)
+
+    def _tokenizer_outputs(self, n_rec: int, n_heap: int):
+        """What a tokenizer's emit pass fills: ``(records, rec_line, rec_alt,`` the nine
+        output arguments of ``avdb_vcf_emit*`` ``)``."""
         b = RecordBatch(chrom=self.empty(n_rec, torch.uint8), pos=self.empty(n_rec, torch.int32),
                         allele_off=self.empty(n_rec, torch.int64),
                         ref_len=self.empty(n_rec, torch.int32), alt_len=self.empty(n_rec, torch.int32),
@@ -1052,16 +1042,8 @@ class Engine:
                         ext_id=self.empty(n_rec, torch.int64))
         rec_line = self.empty(n_rec, torch.int32)
         rec_alt = self.empty(n_rec, torch.int32)
-        outs = (N.ptr(b.chrom), N.ptr(b.pos), N.ptr(b.allele_off), N.ptr(b.ref_len), N.ptr(b.alt_len),
-                N.ptr(b.ext_id), N.ptr(b.heap), N.ptr(rec_line), N.ptr(rec_alt), s)
-        if n_rec and want_lines:
-            N.check("avdb_vcf_emit", self.lib.avdb_vcf_emit(
-                self.ctx, tp, nb, n_lines, N.ptr(lines), N.ptr(rec_off), N.ptr(heap_off), *outs))
-        elif n_rec:
-            N.check("avdb_vcf_emit_ws", self.lib.avdb_vcf_emit_ws(
-                self.ctx, tp, nb, n_lines, N.ptr(ws), ws.numel(), N.ptr(rec_off), N.ptr(heap_off), *outs))
-        return VcfBatch(text=text_t, n_lines=n_lines, lines=lines, rec_off=rec_off, heap_off=heap_off,
-                        records=b, rec_line=rec_line, rec_alt=rec_alt)
+        return b, rec_line, rec_alt, (b.chrom, b.pos, b.allele_off, b.ref_len, b.alt_len, b.ext_id, b.heap,
+                                      rec_line, rec_alt)
 
     def _vcf_tokenize_local(self, text, vcf_opts):
         """vcf_tokenize(want_lines=False) without the count pass: (batch, device
@@ -1069,42 +1051,24 @@ class Engine:
         caller then takes the counted path on the same device text).  The slot
         workspace (about 2.7x the text: line, record and heap slots, avdb.h) is the
         engine's, reused across calls."""
-        if isinstance(text, (bytes, bytearray, memoryview)):
-            host = bytes(text)
-            t = torch.frombuffer(bytearray(host) if host else bytearray(b"\n"), dtype=torch.uint8)
-            text_t = (t if host else t[:0]).to(self.device)
-        else:
-            text_t = self._dev(text)
+        text_t = self._as_text(text)
         nb = int(text_t.numel())
-        tp = N.ptr(text_t) if nb else None
-        s = self._stream()
-        sz = ctypes.c_size_t()
-        self.lib.avdb_vcf_local_workspace_size(nb, ctypes.byref(sz))
-        ws = self.scratch("vcf_local", int(sz.value))
+        tp = text_t if nb else None
+        ws = self.scratch("vcf_local", N.size("avdb_vcf_local_workspace_size", nb))
         tot = torch.zeros(4, dtype=torch.int64, device=self.device)
-        N.check("avdb_vcf_parse_local", self.lib.avdb_vcf_parse_local(
-            self.ctx, tp, nb, N.ptr(ws), ws.numel(), ctypes.byref(vcf_opts) if vcf_opts is not None else None,
-            N.ptr(tot), s))
+        self._launch("avdb_vcf_parse_local", tp, nb, ws, ws.numel(),
+                     ctypes.byref(vcf_opts) if vcf_opts is not None else None, tot)
         n_lines, n_rec, n_heap, overflow = (int(v) for v in tot.cpu().tolist())
         if overflow:
             return None, text_t
-        b = RecordBatch(chrom=self.empty(n_rec, torch.uint8), pos=self.empty(n_rec, torch.int32),
-                        allele_off=self.empty(n_rec, torch.int64),
-                        ref_len=self.empty(n_rec, torch.int32), alt_len=self.empty(n_rec, torch.int32),
-                        heap=self.empty(max(1, n_heap), torch.uint8),
-                        ext_id=self.empty(n_rec, torch.int64))
-        rec_line = self.empty(n_rec, torch.int32)
-        rec_alt = self.empty(n_rec, torch.int32)
+        b, rec_line, rec_alt, outs = self._tokenizer_outputs(n_rec, n_heap)
         rec_off = self.empty(n_lines + 1, torch.int64)
         heap_off = self.empty(n_lines + 1, torch.int64)
         if n_rec == 0:  # (no line has a record: every offset is 0)
             rec_off.zero_()
             heap_off.zero_()
         else:
-            N.check("avdb_vcf_emit_local", self.lib.avdb_vcf_emit_local(
-                self.ctx, tp, nb, N.ptr(ws), ws.numel(), N.ptr(rec_off), N.ptr(heap_off), N.ptr(b.chrom),
-                N.ptr(b.pos), N.ptr(b.allele_off), N.ptr(b.ref_len), N.ptr(b.alt_len), N.ptr(b.ext_id),
-                N.ptr(b.heap), N.ptr(rec_line), N.ptr(rec_alt), s))
+            self._launch("avdb_vcf_emit_local", tp, nb, ws, ws.numel(), rec_off, heap_off, *outs)
         return VcfBatch(text=text_t, n_lines=n_lines, lines=None, rec_off=rec_off, heap_off=heap_off,
                         records=b, rec_line=rec_line, rec_alt=rec_alt), text_t
 
@@ -1115,19 +1079,14 @@ class Engine:
         from .shard import piece_table
         base, count, prank = piece_table(assignment, self.lengths, cut)
         n = vb.n_lines
-        sz = ctypes.c_size_t()
-        self.lib.avdb_shard_workspace_size(n, ctypes.byref(sz))
-        ws = self.empty(max(1, int(sz.value)), torch.uint8)
+        ws = self.empty(max(1, N.size("avdb_shard_workspace_size", n)), torch.uint8)
         sel = self.empty(n + 1, torch.int64)
-        s = self._stream()
-        N.check("avdb_vcf_select_lines", self.lib.avdb_vcf_select_lines(
-            self.ctx, n, N.ptr(vb.lines), base.ctypes.data, count.ctypes.data, prank.ctypes.data, len(prank),
-            int(cut), int(rank), N.ptr(ws), ws.numel(), N.ptr(sel), s))
+        self._launch("avdb_vcf_select_lines", n, vb.lines, base, count, prank, len(prank), int(cut), int(rank),
+                     ws, ws.numel(), sel)
         total = int(sel[n].item())
         out = self.empty(max(1, total), torch.uint8)
         if total:
-            N.check("avdb_vcf_select_copy", self.lib.avdb_vcf_select_copy(
-                self.ctx, N.ptr(vb.text), vb.text.numel(), n, N.ptr(vb.lines), N.ptr(sel), N.ptr(out), s))
+            self._launch("avdb_vcf_select_copy", vb.text, vb.text.numel(), n, vb.lines, sel, out)
         return out[:total]
 
     # -- K5: COPY rows / .mapping lines / display attributes --------------------
@@ -1140,9 +1099,9 @@ class Engine:
         """The load driver's COPY buffer and .mapping text for ``vb``'s lines
         (K5b: size pass, scans, one host sync for the totals, write pass)."""
         n = vb.n_lines
-        s = self._stream()
-        tp = N.ptr(vb.text) if vb.text.numel() else None
-        opts = N.FormatOpts(str(alg_id).encode(), int(max_seq_len), N.FORMAT_ADSP if adsp else 0)
+        self._stream()  # (a host-only engine stops here, before any argument check)
+        tp = vb.text if vb.text.numel() else None
+        opts =N.FormatOpts(str(alg_id).encode(), int(max_seq_len), N.FORMAT_ADSP if adsp else 0)
         if adsp_dup is not None:  # ADSP: records whose primary key is already loaded
             opts.adsp_dup = N.ptr(adsp_dup)
         if existing is not None:  # (match, kind, frag, frag_off) device tensors from keyset_probe
@@ -1150,31 +1109,24 @@ class Engine:
             opts.match, opts.match_kind, opts.frag, opts.frag_off = N.ptr(m), N.ptr(k), N.ptr(fr), N.ptr(fo)
         if len(opts.alg_id) >= N.MAX_ALG_ID:
             raise ValueError("algorithm id too long")
-        sz = ctypes.c_size_t()
-        self.lib.avdb_format_workspace_size(n, ctypes.byref(sz))
-        ws = self.empty(int(sz.value), torch.uint8)
+        ws = self.empty(N.size("avdb_format_workspace_size", n), torch.uint8)
         copy_off = self.empty(n + 1, torch.int64)
         map_off = self.empty(n + 1, torch.int64)
         state = self.empty(max(1, n), torch.uint8)
         if end.numel() == 0:  # no records in this batch: the kernels never read them
             end = code = self.empty(1, torch.int32)
             status = self.empty(1, torch.uint8)
-        dg = None if digest is None else N.ptr(digest)
-        kp = None if keep is None else N.ptr(keep)
-        args = (self.ctx, tp, vb.text.numel(), n, N.ptr(vb.lines), N.ptr(vb.rec_off), N.ptr(end), N.ptr(code),
-                N.ptr(status), dg, kp, ctypes.byref(opts))
+        args = (tp, vb.text.numel(), n, vb.lines, vb.rec_off, end, code, status, digest, keep, ctypes.byref(opts))
         ev = _Timer(events, self.device)
         ev.start("format_size")
-        N.check("avdb_vcf_format_size", self.lib.avdb_vcf_format_size(
-            *args, N.ptr(ws), ws.numel(), N.ptr(copy_off), N.ptr(map_off), N.ptr(state), s))
+        self._launch("avdb_vcf_format_size", *args, ws, ws.numel(), copy_off, map_off, state)
         ev.stop()
         tot = torch.stack([copy_off[n], map_off[n]]).cpu().tolist()
         copy = self.empty(max(8, int(tot[0])), torch.uint8)
         mapping = self.empty(max(8, int(tot[1])), torch.uint8)
         ctr = counters if counters is not None else self.new_counters()
         ev.start("format_write")
-        N.check("avdb_vcf_format_write", self.lib.avdb_vcf_format_write(
-            *args, N.ptr(copy_off), N.ptr(map_off), N.ptr(state), N.ptr(copy), N.ptr(mapping), N.ptr(ctr), s))
+        self._launch("avdb_vcf_format_write", *args, copy_off, map_off, state, copy, mapping, ctr)
         ev.stop()
         return FormatResult(copy=copy[: int(tot[0])], mapping=mapping[: int(tot[1])], copy_off=copy_off,
                             map_off=map_off, line_state=state[:n], counters=ctr)
@@ -1182,23 +1134,18 @@ class Engine:
     def display_attributes(self, b: RecordBatch, end: torch.Tensor):
         """K5a: json.dumps(get_display_attributes()) per record.  Returns
         ``(text uint8, off int64[n+1], state uint8[n])`` device tensors."""
-        b = b if b.device == self.device else b.to(self.device)
-        self._check_alleles(b)
+        b = self._batch(b)
         n = b.n
-        s = self._stream()
-        sz = ctypes.c_size_t()
-        self.lib.avdb_format_workspace_size(n, ctypes.byref(sz))
-        ws = self.empty(int(sz.value), torch.uint8)
+        ws = self.empty(N.size("avdb_format_workspace_size", n), torch.uint8)
         off = self.empty(n + 1, torch.int64)
         state = self.empty(max(1, n), torch.uint8)
         end = self._dev(end)
-        args = (self.ctx, N.ptr(b.chrom), N.ptr(b.pos), N.ptr(end), N.ptr(b.allele_off), N.ptr(b.ref_len),
-                N.ptr(b.alt_len), N.ptr(b.heap), b.heap.numel(), n, N.ptr(ws), ws.numel(), N.ptr(off))
-        N.check("avdb_display_attributes", self.lib.avdb_display_attributes(*args, None, N.ptr(state), s))
+        args = (b.chrom, b.pos, end, b.allele_off, b.ref_len, b.alt_len, b.heap, b.heap.numel(), n, ws, ws.numel(), off)
+        self._launch("avdb_display_attributes", *args, None, state)
         total = int(off[n].item())
         out = self.empty(max(8, total), torch.uint8)
         if n:
-            N.check("avdb_display_attributes", self.lib.avdb_display_attributes(*args, N.ptr(out), N.ptr(state), s))
+            self._launch("avdb_display_attributes", *args, out, state)
         return out[:total], off, state[:n]
 
     # -- K7: primary keys + bin paths as text ------------------------------------
@@ -1216,10 +1163,9 @@ class Engine:
         ``digest``): long records' keys are laid out with their 32 digest
         characters left for :meth:`fill_digests` (state ``KEY_DIGEST_PENDING``),
         so this launch need not wait for K4."""
-        b = b if b.device == self.device else b.to(self.device)
-        self._check_alleles(b)
+        b = self._batch(b)
         n = b.n
-        s = self._stream()
+        self._stream()  # (a host-only engine stops here, before any argument check)
         code = self._dev(code)
         digest = self._dev(digest)
         if defer_digest and (digest is not None or not onepass):
@@ -1227,9 +1173,8 @@ class Engine:
         if onepass:
             return self._primary_keys_onepass(b, code, digest, max_seq_len, out, defer_digest)
         if out is None:
-            sz = ctypes.c_size_t()
-            self.lib.avdb_format_workspace_size(n, ctypes.byref(sz))
-            out = KeyText(ws=self.empty(int(sz.value), torch.uint8), key_off=self.empty(n + 1, torch.int64),
+            out = KeyText(ws=self.empty(N.size("avdb_format_workspace_size", n), torch.uint8),
+                          key_off=self.empty(n + 1, torch.int64),
                           path_off=self.empty(n + 1, torch.int64) if code is not None else None,
                           state=self.empty(max(1, n), torch.uint8), keys=None, paths=None)
         if out.off32:
@@ -1237,18 +1182,16 @@ class Engine:
         if out.key_off.numel() < n + 1 or out.state.numel() < max(1, n) or \
                 (code is not None and (out.path_off is None or out.path_off.numel() < n + 1)):
             raise ValueError("primary_keys: the reused KeyText holds fewer records (or no paths)")
-        args = (self.ctx, N.ptr(b.chrom), N.ptr(b.pos), N.ptr(b.allele_off), N.ptr(b.ref_len), N.ptr(b.alt_len),
-                N.ptr(b.heap), b.heap.numel(), N.ptr(b.ext_id), N.ptr(code), N.ptr(digest), n, int(max_seq_len),
-                N.ptr(out.ws), out.ws.numel(), N.ptr(out.key_off), N.ptr(out.path_off))
-        N.check("avdb_primary_keys", self.lib.avdb_primary_keys(*args, None, 0, None, 0, None, s))
+        args = (*b.soa(), b.ext_id, code, digest, n, int(max_seq_len), out.ws, out.ws.numel(), out.key_off,
+                out.path_off)
+        self._launch("avdb_primary_keys", *args, None, 0, None, 0, None)
         if out.keys is None:
             tot = torch.stack([out.key_off[n], out.path_off[n] if code is not None else out.key_off[n]]).cpu().tolist()
             out.keys = self.empty(max(8, int(tot[0])), torch.uint8)
             out.paths = self.empty(max(8, int(tot[1])), torch.uint8) if code is not None else None
         if n:
-            N.check("avdb_primary_keys", self.lib.avdb_primary_keys(
-                *args, N.ptr(out.keys), out.keys.numel(), N.ptr(out.paths),
-                out.paths.numel() if out.paths is not None else 0, N.ptr(out.state), s))
+            self._launch("avdb_primary_keys", *args, out.keys, out.keys.numel(), out.paths,
+                         out.paths.numel() if out.paths is not None else 0, out.state)
         return out
 
     def new_key_text(self, n: int, heap_bytes: int, paths: bool = True, off32: bool = False) -> "KeyText":
@@ -1257,17 +1200,15 @@ class Engine:
         its group totals into before the first ``primary_keys(..., out=...)``.
         ``off32``: the offsets in the narrow layout (AVDB_KEYS_OFF32, for exactly
         ``n`` records)."""
-        sz = ctypes.c_size_t()
-        self.lib.avdb_primary_keys_onepass_workspace_size(n, ctypes.byref(sz))
+        ws_bytes = N.size("avdb_primary_keys_onepass_workspace_size", n)
         kc, pc = ctypes.c_size_t(), ctypes.c_size_t()
-        self.lib.avdb_primary_keys_bound(n, heap_bytes, ctypes.byref(kc), ctypes.byref(pc))
+        N.call("avdb_primary_keys_bound", n, heap_bytes, ctypes.byref(kc), ctypes.byref(pc))
         if off32:
-            ob = ctypes.c_size_t()
-            self.lib.avdb_keys_off32_bytes(n, ctypes.byref(ob))
-            mk = lambda: self.empty(int(ob.value), torch.uint8)  # noqa: E731
+            ob = N.size("avdb_keys_off32_bytes", n)
+            mk = lambda: self.empty(ob, torch.uint8)  # noqa: E731
         else:
             mk = lambda: self.empty(n + 1, torch.int64)  # noqa: E731
-        return KeyText(ws=self.empty(int(sz.value), torch.uint8), key_off=mk(), path_off=mk() if paths else None,
+        return KeyText(ws=self.empty(ws_bytes, torch.uint8), key_off=mk(), path_off=mk() if paths else None,
                        state=self.empty(max(16, n), torch.uint8), keys=self.empty(int(kc.value), torch.uint8),
                        paths=self.empty(int(pc.value), torch.uint8) if paths else None, off32=off32)
 
@@ -1278,9 +1219,7 @@ class Engine:
         b = b if b.device == self.device else b.to(self.device)
         if kt.off32:
             raise ValueError("fill_digests: narrow key offsets are not accepted")
-        N.check("avdb_primary_keys_fill_digests", self.lib.avdb_primary_keys_fill_digests(
-            self.ctx, N.ptr(b.chrom), N.ptr(b.pos), b.n, N.ptr(digest), N.ptr(kt.key_off), N.ptr(kt.keys),
-            N.ptr(kt.state), self._stream()))
+        self._launch("avdb_primary_keys_fill_digests", b.chrom, b.pos, b.n, digest, kt.key_off, kt.keys, kt.state)
         return kt
 
     def _primary_keys_onepass(self, b: RecordBatch, code, digest, max_seq_len: int, out,
@@ -1290,20 +1229,17 @@ class Engine:
         record's sizes, writes its offsets and the text; the text buffers are sized
         by ``avdb_primary_keys_bound``, so no host sync is needed even the first time."""
         n = b.n
-        sz = ctypes.c_size_t()
-        self.lib.avdb_primary_keys_onepass_workspace_size(n, ctypes.byref(sz))
+        ws_bytes = N.size("avdb_primary_keys_onepass_workspace_size", n)
         if out is None:
             out = self.new_key_text(n, b.heap.numel(), paths=code is not None)
         if out.key_off.numel() < n + 1 or out.state.numel() < max(1, n) or \
                 (code is not None and (out.path_off is None or out.path_off.numel() < n + 1 or out.paths is None)):
             raise ValueError("primary_keys: the reused KeyText holds fewer records (or no paths)")
         if out.off32:
-            ob = ctypes.c_size_t()
-            self.lib.avdb_keys_off32_bytes(n, ctypes.byref(ob))
-            if out.key_off.numel() < ob.value or (code is not None and out.path_off.numel() < ob.value):
+            ob = N.size("avdb_keys_off32_bytes", n)
+            if out.key_off.numel() < ob or (code is not None and out.path_off.numel() < ob):
                 raise ValueError("primary_keys: the narrow offset buffers were made for fewer records")
-        if out.ws.numel() < sz.value:
-            out.ws = self.empty(int(sz.value), torch.uint8)
+        out.ws = self.workspace(ws_bytes, out.ws)
         # the keyed K2 wrote this batch's group totals into this KeyText's workspace
         # (sizes from these length / id arrays and, for the paths, these bin codes)
         tot = self._pending.pop("totals", None)
@@ -1311,12 +1247,9 @@ class Engine:
                  and _stamp_ok(tot[0], out.ws, b.chrom, b.pos, b.ref_len, b.alt_len, b.ext_id, code))
         flags = (N.KEYS_TOTALS_READY if ready else 0) | (N.KEYS_DIGEST_DEFERRED if defer else 0) | \
             (N.KEYS_OFF32 if out.off32 else 0)
-        N.check("avdb_primary_keys_onepass_ex", self.lib.avdb_primary_keys_onepass_ex(
-            self.ctx, N.ptr(b.chrom), N.ptr(b.pos), N.ptr(b.allele_off), N.ptr(b.ref_len), N.ptr(b.alt_len),
-            N.ptr(b.heap), b.heap.numel(), N.ptr(b.ext_id), N.ptr(code), N.ptr(digest), n, int(max_seq_len),
-            N.ptr(out.ws), out.ws.numel(), N.ptr(out.key_off), N.ptr(out.path_off), N.ptr(out.keys), out.keys.numel(),
-            N.ptr(out.paths), out.paths.numel() if out.paths is not None else 0, N.ptr(out.state),
-            flags, self._stream()))
+        self._launch("avdb_primary_keys_onepass_ex", *b.soa(), b.ext_id, code, digest, n, int(max_seq_len), out.ws,
+                     out.ws.numel(), out.key_off, out.path_off, out.keys, out.keys.numel(), out.paths,
+                     out.paths.numel() if out.paths is not None else 0, out.state, flags)
         return out
 
     # -- K6: existing-variant key set ----------------------------------------
@@ -1324,28 +1257,20 @@ class Engine:
         """Hash table over the key strings (``keys`` bytes, ``key_off`` int64[n+1])."""
         keys, key_off = self._dev(keys), self._dev(key_off)
         n = key_off.numel() - 1
-        sz = ctypes.c_size_t()
-        self.lib.avdb_keyset_workspace_size(n, ctypes.byref(sz))
-        table = self.empty(int(sz.value), torch.uint8)
-        N.check("avdb_keyset_build", self.lib.avdb_keyset_build(
-            self.ctx, N.ptr(keys) if keys.numel() else None, N.ptr(key_off), n, N.ptr(table), table.numel(),
-            self._stream()))
+        table = self.empty(N.size("avdb_keyset_workspace_size", n), torch.uint8)
+        self._launch("avdb_keyset_build", keys if keys.numel() else None, key_off, n, table, table.numel())
         return table
 
     def keyset_probe(self, table: torch.Tensor, keys: torch.Tensor, key_off: torch.Tensor, b: RecordBatch,
                      check_alt: bool = True, counters: Optional[torch.Tensor] = None):
         """``(match int32[n], kind uint8[n])``: first equal key of each record's
         metaseq id (then of the switched alleles with ``check_alt``)."""
-        b = b if b.device == self.device else b.to(self.device)
-        self._check_alleles(b)
+        b = self._batch(b)
         n = b.n
         match = self.empty(max(1, n), torch.int32)
         kind = self.empty(max(1, n), torch.uint8)
-        N.check("avdb_keyset_probe", self.lib.avdb_keyset_probe(
-            self.ctx, N.ptr(table), table.numel(), N.ptr(keys) if keys.numel() else None, N.ptr(key_off),
-            key_off.numel() - 1, N.ptr(b.chrom), N.ptr(b.pos), N.ptr(b.allele_off), N.ptr(b.ref_len),
-            N.ptr(b.alt_len), N.ptr(b.heap), b.heap.numel(), n, 1 if check_alt else 0, N.ptr(match), N.ptr(kind),
-            N.ptr(counters), self._stream()))
+        self._launch("avdb_keyset_probe", table, table.numel(), keys if keys.numel() else None, key_off,
+                     key_off.numel() - 1, *b.soa(), n, 1 if check_alt else 0, match, kind, counters)
         return match[:n], kind[:n]
 
     def keyset_probe_text(self, table: torch.Tensor, keys: torch.Tensor, key_off: torch.Tensor,
@@ -1353,14 +1278,14 @@ class Engine:
                           counters: Optional[torch.Tensor] = None) -> torch.Tensor:
         """``match int32[n]``: first key equal to ``q[q_off[i]:q_off[i+1]]``, or -1."""
         match = self.empty(max(1, n), torch.int32)
-        N.check("avdb_keyset_probe_text", self.lib.avdb_keyset_probe_text(
-            self.ctx, N.ptr(table), table.numel(), N.ptr(keys) if keys.numel() else None, N.ptr(key_off),
-            key_off.numel() - 1, N.ptr(q) if q.numel() else None, N.ptr(q_off), N.ptr(skip), n, N.ptr(match),
-            N.ptr(counters), self._stream()))
+        self._launch("avdb_keyset_probe_text", table, table.numel(), keys if keys.numel() else None, key_off,
+                     key_off.numel() - 1, q if q.numel() else None, q_off, skip, n, match, counters)
         return match[:n]
 
     # -- text slabs (K10, K12) ---------------------------------------------------
     def _as_text(self, text) -> torch.Tensor:
+        """Text (bytes-like, numpy ``uint8`` or a ``uint8`` tensor) as a dense tensor on
+        the engine's device; no bytes give an empty tensor (NULL at a call)."""
         if isinstance(text, (bytes, bytearray, memoryview)):
             text = torch.from_numpy(np.frombuffer(bytes(text), dtype=np.uint8).copy()) if len(text) else \
                 torch.zeros(0, dtype=torch.uint8)
@@ -1384,8 +1309,7 @@ class Engine:
             return int((text == 10).sum()) + int(text[-1] != 10)
         ws = self.scratch("text_count", N.VCF_COUNT_WORKSPACE_BYTES)
         cnt = self.empty(1, torch.int64)
-        N.check("avdb_vcf_count_lines", self.lib.avdb_vcf_count_lines(
-            self.ctx, N.ptr(text), nb, N.ptr(ws), ws.numel(), N.ptr(cnt), self._stream()))
+        self._launch("avdb_vcf_count_lines", text, nb, ws, ws.numel(), cnt)
         return int(cnt.item()) + int(text[-1].item() != 10)
 
     # -- K12: the key set's columns from an export --------------------------------
@@ -1408,17 +1332,14 @@ class Engine:
         flags = self.empty(m, torch.uint8)
         row_off = self.empty(m, torch.int64)
         counts = self.empty(N.EXIST_N_COUNTS, torch.int64)
-        tp = N.ptr(text) if nb else None
-        tail = []
-        if not self.host_only:
-            sz = ctypes.c_size_t()
-            self.lib.avdb_existing_workspace_size(nb, n_lines, ctypes.byref(sz))
-            ws = self.scratch("existing_build", int(sz.value))
-            tail = [N.ptr(ws), ws.numel(), self._stream()]
-        size = self.lib.avdb_existing_size_host if self.host_only else self.lib.avdb_existing_size
-        N.check("avdb_existing_size", size(self.ctx, tp, nb, n_lines, existing_contig_mask(contigs), N.ptr(key_len),
-                                           N.ptr(pk_len), N.ptr(frag_len), N.ptr(flags), N.ptr(row_off),
-                                           N.ptr(counts), *tail))
+        tp = text if nb else None
+        if self.host_only:
+            run, suffix, tail = self._call, "_host", ()
+        else:
+            ws = self.scratch("existing_build", N.size("avdb_existing_workspace_size", nb, n_lines))
+            run, suffix, tail = self._launch, "", (ws, ws.numel())
+        run("avdb_existing_size" + suffix, tp, nb, n_lines, existing_contig_mask(contigs), key_len, pk_len, frag_len,
+            flags, row_off, counts, *tail)
         cnt = dict(zip(N.EXIST_COUNTS, (int(x) for x in counts.cpu().numpy().astype(np.uint64))))
         if cnt["lone_cr"]:
             raise ValueError(f"{cnt['lone_cr']} carriage return(s) in the export that no newline follows: Python's "
@@ -1450,17 +1371,13 @@ class Engine:
         frag = self.empty(max(1, frag_bytes), torch.uint8)
         key_off, pk_off, frag_off = (self.empty(n + 1, torch.int64) for _ in range(3))
         totals = self.empty(4, torch.int64)
-        write = self.lib.avdb_existing_write_host if self.host_only else self.lib.avdb_existing_write
-        N.check("avdb_existing_write", write(self.ctx, tp, nb, n_lines, n, N.ptr(key_len), N.ptr(pk_len),
-                                             N.ptr(frag_len), N.ptr(flags), N.ptr(row_off), N.ptr(keys),
-                                             cnt["key_bytes"], N.ptr(key_off), N.ptr(pks), cnt["pk_bytes"],
-                                             N.ptr(pk_off), N.ptr(frag), frag_bytes, N.ptr(frag_off), N.ptr(totals),
-                                             *tail))
+        run("avdb_existing_write" + suffix, tp, nb, n_lines, n, key_len, pk_len, frag_len, flags, row_off, keys,
+            cnt["key_bytes"], key_off, pks, cnt["pk_bytes"], pk_off, frag, frag_bytes, frag_off, totals, *tail)
         if rendered is not None:
             frag[self._spans(frag_off[host_rows], rendered[1])] = rendered[0]
         tot = totals.cpu().tolist()
         if tot[3] or tot[:3] != [cnt["key_bytes"], cnt["pk_bytes"], frag_bytes]:
-            raise N.NativeError("avdb_existing_write", N.AVDB_ERANGE,
+            raise N.NativeError("avdb_existing_write" + suffix, N.AVDB_ERANGE,
                                 f"blob totals {tot[:3]} do not fit the sizes the size pass gave")
         return ExistingColumns(n, keys, key_off, pks, pk_off, frag, frag_off, flags[:n], cnt)
 
@@ -1483,16 +1400,12 @@ class Engine:
         first_row = self.empty(N.CADD_N_CONTIGS, torch.int32)
         end_row = self.empty(N.CADD_N_CONTIGS, torch.int32)
         counts = self.empty(N.CADD_N_COUNTS, torch.int64)
-        args = [self.ctx, N.ptr(text) if nb else None, nb, n_lines] + [N.ptr(c) for c in cols] + \
-               [N.ptr(first_row), N.ptr(end_row), N.ptr(counts)]
+        args = (text if nb else None, nb, n_lines, *cols, first_row, end_row, counts)
         if self.host_only:
-            N.check("avdb_cadd_table_build_host", self.lib.avdb_cadd_table_build_host(*args))
+            self._call("avdb_cadd_table_build_host", *args)
         else:
-            sz = ctypes.c_size_t()
-            self.lib.avdb_cadd_workspace_size(nb, n_lines, ctypes.byref(sz))
-            ws = self.scratch("cadd_build", int(sz.value))
-            N.check("avdb_cadd_table_build", self.lib.avdb_cadd_table_build(
-                *args, N.ptr(ws), ws.numel(), self._stream()))
+            ws = self.scratch("cadd_build", N.size("avdb_cadd_workspace_size", nb, n_lines))
+            self._launch("avdb_cadd_table_build", *args, ws, ws.numel())
         cnt = counts.cpu().numpy().astype(np.uint64)
         n_rows = int(cnt[N.CADD_COUNT_ROWS])
         return CaddColumns(text, n_rows, *[c[:n_rows] for c in cols], first_row, end_row, cnt)
@@ -1505,8 +1418,7 @@ class Engine:
         buffers this call allocates; ``out``: the caller's four buffers, of which
         only the first ``n`` entries are touched).  ``counters``: see
         :meth:`new_cadd_counters`."""
-        b = b if b.device == self.device else b.to(self.device)
-        self._check_alleles(b)
+        b = self._batch(b)
         n = b.n
         for t in (snv, indel):
             if t is not None and t.text.device != self.device:
@@ -1523,13 +1435,12 @@ class Engine:
                 raise ValueError("out buffers must hold n entries on the engine's device")
         vs = snv.view() if snv is not None else None
         vi = indel.view() if indel is not None else None
-        args = [self.ctx, ctypes.byref(vs) if vs is not None else None, ctypes.byref(vi) if vi is not None else None,
-                N.ptr(b.chrom), N.ptr(b.pos), N.ptr(b.allele_off), N.ptr(b.ref_len), N.ptr(b.alt_len), N.ptr(b.heap),
-                b.heap.numel(), n, N.ptr(row), N.ptr(kind), N.ptr(raw), N.ptr(phred), N.ptr(counters)]
+        args = (ctypes.byref(vs) if vs is not None else None, ctypes.byref(vi) if vi is not None else None,
+                *b.soa(), n, row, kind, raw, phred, counters)
         if self.host_only:
-            N.check("avdb_cadd_match_host", self.lib.avdb_cadd_match_host(*args))
+            self._call("avdb_cadd_match_host", *args)
         else:
-            N.check("avdb_cadd_match", self.lib.avdb_cadd_match(*args, self._stream()))
+            self._launch("avdb_cadd_match", *args)
         return row[:n], kind[:n], raw[:n], phred[:n]
 
     # -- K11: BGZF input ---------------------------------------------------------
@@ -1560,9 +1471,8 @@ class Engine:
         n, consumed, out_bytes = ctypes.c_size_t(), ctypes.c_size_t(), ctypes.c_uint64()
         while True:
             in_off, out_off = np.empty(cap, dtype=np.uint64), np.empty(cap + 1, dtype=np.uint64)
-            rc = self.lib.avdb_bgzf_index_host(a.ctypes.data + at if nb else None, nb - at, cap, in_off.ctypes.data,
-                                               out_off.ctypes.data, ctypes.byref(n), ctypes.byref(consumed),
-                                               ctypes.byref(out_bytes))
+            rc = N.call("avdb_bgzf_index_host", a.ctypes.data + at if nb else None, nb - at, cap, in_off, out_off,
+                        ctypes.byref(n), ctypes.byref(consumed), ctypes.byref(out_bytes), check=False)
             if rc == N.AVDB_ENOTBGZF and at == 0:
                 raise NotBgzf(N.last_error())
             if rc < 0:
@@ -1623,12 +1533,11 @@ class Engine:
         counts = self.empty(N.BGZF_N_COUNTS, torch.int64)
         d_in = torch.from_numpy(in_off.view(np.int64)).to(self.device, non_blocking=True)
         d_out = torch.from_numpy(out_off.view(np.int64)).to(self.device, non_blocking=True)
-        args = [self.ctx, N.ptr(comp) if nb else None, nb, N.ptr(d_in) if n else None, N.ptr(d_out), n, N.ptr(out),
-                total, N.ptr(status), N.ptr(counts)]
+        args = (comp if nb else None, nb, d_in if n else None, d_out, n, out, total, status, counts)
         if self.host_only:
-            N.check("avdb_bgzf_inflate_host", self.lib.avdb_bgzf_inflate_host(*args))
+            self._call("avdb_bgzf_inflate_host", *args)
         else:
-            N.check("avdb_bgzf_inflate", self.lib.avdb_bgzf_inflate(*args, self._stream()))
+            self._launch("avdb_bgzf_inflate", *args)
         cnt = counts.cpu().numpy().astype(np.uint64)  # (the sync: comp, d_in and d_out are done with)
         if not raise_on_error:
             return out[:total], status[:n], cnt
@@ -1640,7 +1549,7 @@ class Engine:
     # -- formatting (host) ---------------------------------------------------
     def format_path(self, chrom_code: int, code: int) -> Optional[str]:
         buf = ctypes.create_string_buffer(N.MAX_PATH)
-        rc = self.lib.avdb_format_bin_path(self.ctx, chrom_code, code & 0xFFFFFFFF, buf, N.MAX_PATH)
+        rc = N.call("avdb_format_bin_path", self.ctx, chrom_code, code & 0xFFFFFFFF, buf, N.MAX_PATH, check=False)
         if rc < 0:
             return None
         return buf.raw[:rc].decode("ascii")
@@ -1654,9 +1563,7 @@ class Engine:
         cap = max(1, n * 88)
         out = np.empty(cap, dtype=np.uint8)
         offs = np.empty(n + 1, dtype=np.uint64)
-        N.check("avdb_format_bin_paths", self.lib.avdb_format_bin_paths(
-            self.ctx, chrom_codes.ctypes.data, codes.ctypes.data, n, out.ctypes.data, cap,
-            offs.ctypes.data))
+        self._call("avdb_format_bin_paths", chrom_codes, codes, n, out, cap, offs)
         raw = out[: int(offs[n])].tobytes().decode("ascii")
         res: List[Optional[str]] = []
         for i in range(n):

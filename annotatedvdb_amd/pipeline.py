@@ -38,12 +38,12 @@ caller's loop.
 
 from __future__ import annotations
 
-import ctypes
 from typing import Dict, Optional
 
 import torch
 
 from . import _native as N
+from .engine import dedup_list_bytes
 
 LAYOUTS = ("onepass", "serial", "fork", "overlap")
 # what bench.py times for C4k (AVDB_BENCH_LAYOUT overrides there) and what
@@ -88,21 +88,17 @@ class KeyedStep:
             narrow_offsets = layout in ("serial", "fork")
         self.kt = engine.new_key_text(n, int(batch.heap.numel()), paths=True, off32=bool(narrow_offsets))
         # K3 list workspace (+ 2^22 entries: the keyed K2's per-workgroup suspect slices round up)
-        self.ws3 = engine.empty(16384 + 4 * (((n + 3) & ~3) + (1 << 22)), torch.uint8)
+        self.ws3 = engine.empty(dedup_list_bytes(n, 1 << 22), torch.uint8)
         self.ws4 = None
         if self.digests:
-            sz = ctypes.c_size_t()
-            engine.lib.avdb_vrs_digest_workspace_size(n, ctypes.byref(sz))
-            self.ws4 = engine.empty(int(sz.value), torch.uint8)
+            self.ws4 = engine.empty(N.size("avdb_vrs_digest_workspace_size", n), torch.uint8)
         # both grid options every time (0 = the library's default), so a capped grid
         # from an earlier step on this engine never carries over
         engine.set_option(N.OPT_K4_GRID, int(k4_grid))
         engine.set_option(N.OPT_K7_GRID, int(k7_grid))
         self.ws_op = None
         if layout == "onepass":
-            sz = ctypes.c_size_t()
-            engine.lib.avdb_keyed_prep_workspace_size(n, ctypes.byref(sz))
-            self.ws_op = engine.empty(int(sz.value), torch.uint8)
+            self.ws_op = engine.empty(N.size("avdb_keyed_prep_workspace_size", n), torch.uint8)
         self.side = torch.cuda.Stream(dev) if layout in ("fork", "overlap") else None
         self.out: Dict[str, object] = {}
 
@@ -188,10 +184,8 @@ class PrepStep:
         self.eng, self.b, self.max_seq_len = engine, batch, int(max_seq_len)
         self.hist, self.counters = hist, counters
         n = batch.n
-        self.ws3 = engine.empty(16384 + 4 * (((n + 3) & ~3) + (1 << 22)), torch.uint8)
-        sz = ctypes.c_size_t()
-        engine.lib.avdb_vrs_digest_workspace_size(n, ctypes.byref(sz))
-        self.ws4 = engine.empty(int(sz.value), torch.uint8)
+        self.ws3 = engine.empty(dedup_list_bytes(n, 1 << 22), torch.uint8)  # (slack: as in KeyedStep)
+        self.ws4 = engine.empty(N.size("avdb_vrs_digest_workspace_size", n), torch.uint8)
         self.out: Dict[str, object] = {}
 
     def run(self, events: Optional[dict] = None) -> Dict[str, object]:

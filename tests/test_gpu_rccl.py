@@ -26,6 +26,11 @@ def test_hist_allgather_c_abi_world_of_one(engine):
         nh, nc = ex.allgather(hist[:7].contiguous(), ctr[:3].contiguous())
         torch.cuda.synchronize()
         assert torch.equal(nh, hist[:7]) and torch.equal(nc, ctr[:3])
+        # a strided view is refused by the call path, under the entry's name
+        with pytest.raises(ValueError, match="avdb_hist_allgather: argument 2 "):
+            ex.allgather(hist[::2], ctr)
+        with pytest.raises(ValueError, match="avdb_hist_allgather: argument 4 "):
+            ex.allgather(hist, ctr[::2])
     finally:
         ex.close()
 
