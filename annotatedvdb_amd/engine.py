@@ -218,6 +218,7 @@ VCF_CHROM_HOST = 0x080
 VCF_EMPTY = 0x100
 VCF_ID_HOST = 0x200
 VCF_HOST_FLAGS = VCF_BAD_POS | VCF_EXT_HOST | VCF_CHROM_HOST | VCF_ID_HOST
+VCF_UNPARSED_FLAGS = VCF_FEW_FIELDS | VCF_EMPTY  # K0 stopped before the fields: no CHROM, POS, ID or records
 
 
 def _stamp(*ts) -> tuple:
@@ -253,12 +254,22 @@ class VcfBatch:
     rec_line: torch.Tensor       # int32[n_rec]
     rec_alt: torch.Tensor
 
-    def lines_host(self) -> np.ndarray:
+    def lines_host(self, rows=None) -> np.ndarray:
+        """The line table on the host, as ``VCF_LINE_DTYPE`` records; ``rows`` (line
+        indices) takes only those lines: gathered on the device, then one copy."""
         if self.lines is None:
             raise ValueError("this batch was tokenized without its line table (want_lines=False)")
         if self.n_lines == 0:
             return np.zeros(0, dtype=VCF_LINE_DTYPE)
-        return self.lines.cpu().numpy()[: self.n_lines * 80].view(VCF_LINE_DTYPE)
+        t = self.lines[: self.n_lines * VCF_LINE_DTYPE.itemsize]
+        if rows is not None:
+            t = t.view(self.n_lines, -1)[torch.as_tensor(rows, dtype=torch.int64, device=t.device)]
+        return t.cpu().numpy().reshape(-1).view(VCF_LINE_DTYPE)
+
+    def line_flags(self) -> torch.Tensor:
+        """The table's ``flags`` column on the device (a strided int32 view)."""
+        t = self.lines[: self.n_lines * VCF_LINE_DTYPE.itemsize].view(torch.int32)
+        return t.view(self.n_lines, -1)[:, VCF_LINE_DTYPE.fields["flags"][1] // 4]
 
 
 class _Timer:

@@ -18,8 +18,10 @@ does the same for a whole batch with one pass of the GPU kernels:
 the COPY rows and the .mapping lines as text on the device; lines the GPU does
 not render byte-exact are rendered here, in place.
 
-``parse_variant`` is ``parse_variants([line])``: one code path, one set of
-semantics.  Exceptions match the reference at the same record: ``ValueError``
+``parse_variant`` tries the per-line host entries first, K5h (the whole line in
+one library call) then K8h (host parse + one call for the line's alts); a line
+neither settles takes the general path, ``parse_variants([line])``.
+Exceptions match the reference at the same record: ``ValueError``
 when a key cannot be built (e.g. ``':'`` inside an allele breaks
 ``metaseqId.split(':')``, primary_key_generator.py:106, through the retry
 ladder :234-256), ``TypeError`` when the location has no bin
@@ -46,11 +48,12 @@ from __future__ import annotations
 import logging
 import re
 from io import StringIO
-from typing import Dict, List, Optional, Sequence
+from dataclasses import dataclass
+from typing import Dict, List, NamedTuple, Optional, Sequence
 
 import numpy as np
 
-from .chromosomes import UNKNOWN_CHROM, bin_index_chrom_code
+from .chromosomes import bin_index_chrom_code
 from .parsers import VcfEntryParser, _xstr
 
 REQUIRED_COPY_FIELDS = ["chromosome", "record_primary_key", "position", "metaseq_id", "bin_index",
@@ -60,10 +63,6 @@ ALLOWABLE_COPY_FIELDS = ["chromosome", "record_primary_key", "position", "is_mul
                          "allele_frequencies", "cadd_scores", "adsp_most_severe_consequence",
                          "adsp_ranked_consequences", "loss_of_function", "vep_output", "adsp_qc",
                          "gwas_flags", "other_annotation", "row_algorithm_id"]
-
-
-class _AltError(Exception):
-    pass
 
 
 _ALG_INVOCATION_PROVIDER = None
@@ -140,6 +139,40 @@ _KEY_OK = 0       # AVDB_KEY_OK
 _CHROM_CODES: Dict[str, int] = {}
 
 
+def _chrom_code(label) -> int:
+    """A label's u8 chromosome code in the device records (255: no bin), cached."""
+    label = str(label)
+    code = _CHROM_CODES.get(label)
+    if code is None:
+        code = _CHROM_CODES[label] = min(bin_index_chrom_code(label), 255)
+    return code
+
+
+def _mapping_text(result) -> str:
+    """One line's result dict as the load driver prints it (load_vcf_file.py:116-117)."""
+    return "".join("%s\t%s\n" % kv for kv in result.items())
+
+
+@dataclass(slots=True)
+class _AltRecord:
+    """One alt allele (ALT != '.') of a parsed line, in record order."""
+    line: int                       # index into ``parsed``
+    alt: str
+    metaseq: str
+    pk_error: Optional[Exception]   # the ValueError its primary key raises, once known
+    variant: object                 # the line's variant namespace
+
+
+class _Prep(NamedTuple):
+    """What ``_gpu_prep`` / ``_small_prep`` hand to ``_emit``, one entry per record."""
+    paths: list
+    pks: list
+    keep: Optional[np.ndarray]            # None: no dedup
+    disp: list
+    match: Optional[np.ndarray] = None    # None: no --skipExisting key set
+    adsp_dup: Optional[Sequence] = None   # None: no ADSP key check
+
+
 class VCFVariantLoader(object):
     """GPU-backed drop-in for the reference ``VCFVariantLoader``'s record prep."""
 
@@ -166,8 +199,6 @@ class VCFVariantLoader(object):
         self._update_existing = False
         self._vcf_header_fields = None
         self.last_load_stats = None
-        self._match = None
-        self._adsp_dup = None
         self._cursor = None
         self._batch_update = False
         self._update_sql = None
@@ -555,8 +586,8 @@ class VCFVariantLoader(object):
             if not (0 < pos < 4294967296):
                 return _SLOW
             code = _CHROM_CODES.get(chrom)
-            if code is None:
-                code = _CHROM_CODES[chrom] = min(bin_index_chrom_code(chrom), 255)
+            if code is None:  # (the cache is read here: no call on the per-line path)
+                code = _chrom_code(chrom)
             rb = ref.encode()
             res = self._engine.small().run([code] * n, [pos] * n, refs=[rb] * n, alts=[a.encode() for a in alts],
                                            ext=[ext] * n, want=7, max_seq_len=self._pk_generator.max_sequence_length())
@@ -650,7 +681,7 @@ class VCFVariantLoader(object):
         from .engine import ExtIdInterner, pack_records
         eng = self._engine
         interner = ExtIdInterner()
-        codes = np.asarray([min(bin_index_chrom_code(r[0]), 255) for r in recs], dtype=np.uint8)
+        codes = np.asarray([_chrom_code(r[0]) for r in recs], dtype=np.uint8)
         pos = [int(r[1]) for r in recs]
         db = pack_records(codes, pos, [str(r[2]).encode() for r in recs], [str(r[3]).encode() for r in recs],
                           [interner.key(r[4]) for r in recs]).to(eng.device)
@@ -673,17 +704,10 @@ class VCFVariantLoader(object):
         ends = d_end.cpu().numpy().view(np.uint32)
         paths = eng.format_paths(codes, d_code.cpu().numpy())
         items = [("%s:%s:%s:%s" % (r[0], r[1], r[2], r[3]), r[4]) for r in recs]
-        try:
-            pks: List = list(self._pk_generator.generate_primary_keys(items))
-        except ValueError:
-            pks = []
-            for it in items:  # isolate the failing records
-                try:
-                    pks.append(self._pk_generator.generate_primary_keys([it])[0])
-                except ValueError as err:
-                    if errors == "raise":
-                        raise
-                    pks.append(err)
+        pks = self._primary_keys(items)
+        err = next((pk for pk in pks if isinstance(pk, Exception)), None)
+        if errors == "raise" and err is not None:
+            raise err
         return [pk if isinstance(pk, Exception) else (int(ends[i]), paths[i], pk, bool(keep[i]))
                 for i, pk in enumerate(pks)]
 
@@ -700,13 +724,12 @@ class VCFVariantLoader(object):
                 parsed.append(("error", ValueError("Must set VariantLoader resume_afer_variant if resuming load")))
                 break
             try:
-                entry = VcfEntryParser(line, self._vcf_header_fields) if isinstance(line, str) else line
-                if not self.resume_load():
+                resuming = not self.resume_load()
+                entry, variant = self._host_variant(line, entry_only=resuming)
+                if resuming:
                     self._update_resume_status(entry.get("id"))
                     parsed.append(("skip",))
                     continue
-                entry.update_chromosome(self._chromosome_map)
-                variant = entry.get_variant(dbSNP=self.is_dbsnp(), namespace=True)
                 parsed.append((entry, variant))
             except Exception as err:  # noqa: BLE001 — re-raised in phase 3
                 parsed.append(("error", err))
@@ -715,18 +738,16 @@ class VCFVariantLoader(object):
 
         # ---- phase 2: per-alt records -> GPU --------------------------------
         recs = self._records_of(parsed)
-        db = codes = None
-        small = None
+        db = codes = small = None
         if recs:
             from .engine import ExtIdInterner, pack_records
             from . import _native as N
             interner = ExtIdInterner()
-            codes = np.asarray([min(bin_index_chrom_code(r[5].chromosome), 255) for r in recs],
-                               dtype=np.uint8)
-            pos = [r[5].position for r in recs]
-            refs = [r[5].ref_allele.encode() for r in recs]
-            alts = [r[1].encode() for r in recs]
-            ext = [interner.key(r[5].ref_snp_id) for r in recs]
+            codes = np.asarray([_chrom_code(r.variant.chromosome) for r in recs], dtype=np.uint8)
+            pos = [r.variant.position for r in recs]
+            refs = [r.variant.ref_allele.encode() for r in recs]
+            alts = [r.alt.encode() for r in recs]
+            ext = [interner.key(r.variant.ref_snp_id) for r in recs]
             if not dedup and keep_override is None and self._existing is None and all(0 < p < 2 ** 32 for p in pos):
                 # the per-line drop-in path: K2 + K7 + K5a in one launch (K8), no copies
                 small = self._engine.small().run(
@@ -735,12 +756,10 @@ class VCFVariantLoader(object):
                     max_seq_len=self._pk_generator.max_sequence_length())
             if small is None:
                 db = pack_records(codes, pos, refs, alts, ext).to(self._engine.device)
-        if small is not None:
-            paths, pks, keep, disp = self._small_prep(recs, small)
-        else:
-            paths, pks, keep, disp = self._gpu_prep(recs, db, codes, dedup, keep_override)
+        prep = self._small_prep(recs, small) if small is not None else \
+            self._gpu_prep(recs, db, codes, dedup, keep_override)
         # ---- phase 3: emit in order --------------------------------------------
-        return self._emit(parsed, recs, paths, pks, keep, disp, errors)
+        return self._emit(parsed, recs, prep, errors)
 
     def parse_vcf_text(self, text, errors: str = "raise", dedup: bool = False):
         """``parse_variants`` for raw VCF text, tokenized on the GPU (K0).
@@ -750,7 +769,7 @@ class VCFVariantLoader(object):
         line.  Text the GPU does not canonicalise (flagged lines) is parsed by
         ``VcfEntryParser`` for those lines only."""
         from .engine import (VCF_COMMENT, VCF_HOST_FLAGS, VCF_ID_METASEQ, VCF_ID_RS, VCF_INFO_RS,
-                             ExtIdInterner)
+                             VCF_UNPARSED_FLAGS)
         from .chromosomes import CHROM_NAMES
         from types import SimpleNamespace
         if self._bin_indexer is None or self._pk_generator is None:
@@ -763,14 +782,15 @@ class VCFVariantLoader(object):
         eng = self._engine
         vb = eng.vcf_tokenize(raw, vo)
         L = vb.lines_host()
+        # K0 lines with host-resolved fields: parsed here, their device records patched
+        flagged = np.nonzero(((L["flags"] & VCF_HOST_FLAGS) != 0) & ((L["flags"] & VCF_COMMENT) == 0))[0]
+        hosted = self._patch_host_records(raw, vb, flagged.tolist(), L[flagged])
         db = vb.records
         rec_line = vb.rec_line.cpu().numpy()
-        codes = db.chrom.cpu().numpy().copy()
+        codes = db.chrom.cpu().numpy()
         # ---- phase 1: per-line variant views from the line table ---------------
         parsed = []
         line_idx = []          # data-line index -> parsed index
-        host_patch = {}        # line -> (chrom code, pos, ext key)
-        interner = ExtIdInterner()
         stop = False
         for li in range(vb.n_lines):
             rec = L[li]
@@ -785,13 +805,10 @@ class VCFVariantLoader(object):
             line = raw[st:st + int(rec["len"])].decode("utf-8")
             code = int(rec["chrom"])
             try:
-                if fl & (VCF_HOST_FLAGS | 0x102) or code == 255 or int(rec["n_rec"]) == 0:
-                    entry = VcfEntryParser(line, self._vcf_header_fields)
-                    entry.update_chromosome(self._chromosome_map)
-                    v = entry.get_variant(dbSNP=self.is_dbsnp(), namespace=True)
-                    if fl & VCF_HOST_FLAGS:
-                        host_patch[li] = (min(bin_index_chrom_code(v.chromosome), 255), v.position,
-                                          interner.key(v.ref_snp_id))
+                if li in hosted:
+                    p = hosted[li]
+                elif fl & VCF_UNPARSED_FLAGS or code == 255 or int(rec["n_rec"]) == 0:
+                    p = self._host_variant(line)
                 else:
                     f = rec["field"]
                     ref = line[f[3]:f[4] - 1]
@@ -806,27 +823,17 @@ class VCFVariantLoader(object):
                         rs = None
                     vid = "%s:%d:%s:%s" % (chrom, pos, ref, altf) if fl & VCF_ID_METASEQ else line[f[2]:f[3] - 1]
                     alts = altf.split(",")
-                    v = SimpleNamespace(id=vid, ref_snp_id=rs, ref_allele=ref, alt_alleles=alts,
-                                        is_multi_allelic=len(alts) > 1, chromosome=chrom, position=pos,
-                                        rs_position=None)
-                    entry = _LazyEntry(line)
-                parsed.append((entry, v))
+                    p = (_LazyEntry(line),
+                         SimpleNamespace(id=vid, ref_snp_id=rs, ref_allele=ref, alt_alleles=alts,
+                                         is_multi_allelic=len(alts) > 1, chromosome=chrom, position=pos,
+                                         rs_position=None))
             except Exception as err:  # noqa: BLE001 — re-raised in phase 3
-                parsed.append(("error", err))
-                if errors == "raise":
-                    stop = True
-        # ---- phase 2: records are already on the device; patch host-resolved lines
-        if host_patch:
-            import torch
-            idx = [i for i, l in enumerate(rec_line.tolist()) if l in host_patch]
-            if idx:
-                vals = [host_patch[int(rec_line[i])] for i in idx]
-                it = torch.tensor(idx, dtype=torch.int64, device=eng.device)
-                db.chrom[it] = torch.tensor([v[0] for v in vals], dtype=torch.uint8, device=eng.device)
-                db.pos[it] = torch.tensor([v[1] for v in vals], dtype=torch.int64).to(torch.int32).to(eng.device)
-                db.ext_id[it] = torch.tensor([v[2] if v[2] < (1 << 63) else v[2] - (1 << 64) for v in vals],
-                                             dtype=torch.int64, device=eng.device)
-                codes[idx] = [v[0] for v in vals]
+                p = err
+            if isinstance(p, Exception):
+                p = ("error", p)
+                stop = errors == "raise"
+            parsed.append(p)
+        # ---- phase 2: the device records of the lines that parsed ----------------
         recs = self._records_of(parsed)
         # GPU records map 1:1 onto recs (same line order, ALT != '.'), except for
         # lines that stopped early on a parse error
@@ -838,8 +845,7 @@ class VCFVariantLoader(object):
             db = _select(db, sel)
             codes = codes[keep_rows]
         assert db.n == len(recs), (db.n, len(recs))
-        paths, pks, keep, disp = self._gpu_prep(recs, db if recs else None, codes, dedup)
-        return self._emit(parsed, recs, paths, pks, keep, disp, errors)
+        return self._emit(parsed, recs, self._gpu_prep(recs, db if recs else None, codes, dedup), errors)
 
     def load_vcf_text(self, text, dedup: bool = False, errors: str = "raise",
                       batch_bytes: int = 256 << 20, mapping_out=None) -> str:
@@ -912,20 +918,16 @@ class VCFVariantLoader(object):
             # resume / a header with moved fields / ADSP without a validator (the
             # reference's is_duplicate raises on it): exact per-line semantics
             out = self.parse_variants(_data_lines(raw), errors=errors, dedup=dedup)
-            return "".join("".join("%s\t%s\n" % kv for kv in o.items()) for o in out
-                           if isinstance(o, dict))
+            return "".join(_mapping_text(o) for o in out if isinstance(o, dict))
         eng = self._engine
         vb = eng.vcf_tokenize(raw, vo)
         n = vb.n_lines
         if n == 0:
             return ""
         db = vb.records
-        # K0 lines with host-resolved fields: resolve chrom/pos/refSNP key on the host
-        # before K2/K3 see the records (same as parse_vcf_text)
-        flags = vb.lines[: n * 80].view(torch.int32).view(n, 20)[:, 18]
-        hl = torch.nonzero((flags & VCF_HOST_FLAGS) != 0).squeeze(1).cpu().tolist()
-        if hl:
-            self._patch_host_records(raw, vb, hl)
+        # K0 lines with host-resolved fields: patched before K2/K3 see the records
+        hl = torch.nonzero((vb.line_flags() & VCF_HOST_FLAGS) != 0).squeeze(1).cpu().tolist()
+        self._patch_host_records(raw, vb, hl)
         end, code, status, _ = eng.record_prep(db, want_lcp=False)
         digest = None
         mx = self._pk_generator.max_sequence_length()
@@ -992,9 +994,7 @@ class VCFVariantLoader(object):
             add_gpu_counters()
             return map_raw
         keep_h = keep.cpu().numpy() if keep is not None else None
-        # the host lines' table rows in one transfer
-        Lh = vb.lines[: n * 80].view(n, 80)[torch.from_numpy(host).to(eng.device)].cpu().numpy()
-        Lh = Lh.view(np.uint64).reshape(len(host), 10)
+        Lh = vb.lines_host(host)  # the host lines' table rows in one transfer
         maps = []
         c0 = m0 = 0
         for hi, li in enumerate(host.tolist()):
@@ -1005,8 +1005,8 @@ class VCFVariantLoader(object):
             while u < len(gpu_updates) and gpu_updates[u][0] < li:
                 self._update_buffer.append(gpu_updates[u][1:])
                 u += 1
-            st, ln = int(Lh[hi, 0]), int(Lh[hi, 1] & 0xFFFFFFFF)
-            line = raw[st:st + ln].decode("utf-8")
+            st = int(Lh["start"][hi])
+            line = raw[st:st + int(Lh["len"][hi])].decode("utf-8")
             kov = None if keep_h is None else keep_h[rec_off[li]:rec_off[li + 1]]
             try:
                 res = self.parse_variants([line], errors="raise", keep_override=kov)[0]
@@ -1020,7 +1020,7 @@ class VCFVariantLoader(object):
                     raise
                 maps.append("")
                 continue
-            maps.append("".join("%s\t%s\n" % kv for kv in res.items()))
+            maps.append(_mapping_text(res))
         self._copy_buffer.write(copy_raw[c0:])
         maps.append(map_raw[m0:])
         self._update_buffer.extend(x[1:] for x in gpu_updates[u:])
@@ -1031,16 +1031,15 @@ class VCFVariantLoader(object):
         """Counters of the GPU-rendered lines before line ``upto`` (the failing
         line), from the per-line / per-record arrays."""
         from . import _native as N
-        n = vb.n_lines
-        L = vb.lines_host()
         gl = np.nonzero(state[:upto] == N.LINE_GPU)[0]
+        L = vb.lines_host(gl)
         self.increment_counter("line", len(gl))
         self.increment_counter("variant", copy_text.count("\n"))
         r_end = int(rec_off[upto])
         on_gpu = np.zeros(r_end, dtype=bool)
         for li in gl.tolist():
             on_gpu[int(rec_off[li]):int(rec_off[li + 1])] = True
-        skipped = int((L["n_alt"][gl].astype(np.int64) - L["n_rec"][gl]).sum())
+        skipped = int((L["n_alt"].astype(np.int64) - L["n_rec"]).sum())
         matched = np.zeros(r_end, dtype=bool)
         if match is not None:
             matched = match[:r_end].cpu().numpy() >= 0
@@ -1054,45 +1053,74 @@ class VCFVariantLoader(object):
             dup = (keep[:r_end].cpu().numpy() == 0) & ~matched & ~upd
             self.increment_counter("duplicates", int((dup & on_gpu).sum()))
 
-    def _patch_host_records(self, raw, vb, line_ids):
-        """Host resolution of K0-flagged lines' chrom / pos / refSNP key in the
-        device records (the GPU only canonicalises plain text)."""
+    def _patch_host_records(self, raw, vb, line_ids, rows=None):
+        """Host resolution of K0-flagged lines (the GPU only canonicalises plain
+        text): parses the lines ``line_ids`` (``rows``: their table rows, if the
+        caller holds them) and writes each one's chrom code / pos / refSNP key over
+        its device records.  Returns ``{line: (entry, variant)}``, the exception in
+        place of the pair where the parse raised (those records stay as K0 wrote them)."""
+        out = {}
+        if not len(line_ids):
+            return out
         import torch
         from .engine import ExtIdInterner
-        eng = self._engine
-        db = vb.records
-        n = vb.n_lines
-        Lh = vb.lines[: n * 80].view(torch.uint8).view(n, 80)[torch.tensor(line_ids, device=eng.device)]
-        Lh = Lh.cpu().numpy()
-        rec_off = vb.rec_off[torch.tensor(line_ids, device=eng.device)].cpu().numpy()
-        nrec = vb.rec_off[torch.tensor(line_ids, device=eng.device) + 1].cpu().numpy() - rec_off
+        dev = self._engine.device
+        if rows is None:
+            rows = vb.lines_host(line_ids)
+        ids = torch.tensor(line_ids, dtype=torch.int64, device=dev)
+        rec_off = vb.rec_off[ids].cpu().tolist()
+        rec_end = vb.rec_off[ids + 1].cpu().tolist()
         interner = ExtIdInterner()
-        idx, vals = [], []
-        for k in range(len(line_ids)):
-            w = np.frombuffer(Lh[k].tobytes(), dtype=np.uint64)
-            st, ln = int(w[0]), int(w[1] & 0xFFFFFFFF)
+        idx, vals = [], []  # record index; (chrom code, pos, refSNP key as the int64 the tensor holds)
+        for k, li in enumerate(line_ids):
+            st = int(rows["start"][k])
             try:
-                e = VcfEntryParser(raw[st:st + ln].decode("utf-8"), self._vcf_header_fields)
-                e.update_chromosome(self._chromosome_map)
-                v = e.get_variant(dbSNP=self.is_dbsnp(), namespace=True)
-            except Exception:  # noqa: BLE001 — the host renderer raises it at this line
+                out[li] = self._host_variant(raw[st:st + int(rows["len"][k])].decode("utf-8"))
+            except Exception as err:  # noqa: BLE001 — the caller's to raise or record at this line
+                out[li] = err
                 continue
+            v = out[li][1]
             key = interner.key(v.ref_snp_id)
-            for j in range(int(nrec[k])):
-                idx.append(int(rec_off[k]) + j)
-                vals.append((min(bin_index_chrom_code(v.chromosome), 255), v.position, key))
+            val = (_chrom_code(v.chromosome), v.position, key if key < (1 << 63) else key - (1 << 64))
+            idx += range(rec_off[k], rec_end[k])
+            vals += [val] * (rec_end[k] - rec_off[k])
         if idx:
-            it = torch.tensor(idx, dtype=torch.int64, device=eng.device)
-            db.chrom[it] = torch.tensor([x[0] for x in vals], dtype=torch.uint8, device=eng.device)
-            db.pos[it] = torch.tensor([x[1] for x in vals], dtype=torch.int64).to(torch.int32).to(eng.device)
-            db.ext_id[it] = torch.tensor([x[2] if x[2] < (1 << 63) else x[2] - (1 << 64) for x in vals],
-                                         dtype=torch.int64, device=eng.device)
+            db, it = vb.records, torch.tensor(idx, dtype=torch.int64, device=dev)
+            chrom, pos, ext = zip(*vals)
+            db.chrom[it] = torch.tensor(chrom, dtype=torch.uint8, device=dev)
+            db.pos[it] = torch.tensor(pos, dtype=torch.int64).to(torch.int32).to(dev)
+            db.ext_id[it] = torch.tensor(ext, dtype=torch.int64, device=dev)
+        return out
 
     # ---- shared pieces --------------------------------------------------------
+    def _host_variant(self, line, entry_only=False):
+        """The host parse of one line (a str, or its VcfEntryParser) as this loader is set
+        up: ``(entry, variant)``; ``entry_only`` stops after the field split (``variant`` None)."""
+        entry = VcfEntryParser(line, self._vcf_header_fields) if isinstance(line, str) else line
+        if entry_only:
+            return entry, None
+        entry.update_chromosome(self._chromosome_map)
+        return entry, entry.get_variant(dbSNP=self.is_dbsnp(), namespace=True)
+
+    def _primary_keys(self, items):
+        """The PK generator's keys for ``(metaseq id, refSNP id)`` items, in one
+        call; when that raises ``ValueError``, one call per item to isolate the
+        failing ones.  Per item: the key, or the ``ValueError`` it raised."""
+        gen = self._pk_generator
+        try:
+            return list(gen.generate_primary_keys(items))
+        except ValueError:
+            out = []
+            for it in items:
+                try:
+                    out.append(gen.generate_primary_keys([it])[0])
+                except ValueError as err:
+                    out.append(err)
+            return out
+
     def _records_of(self, parsed):
-        """Per-alt record descriptors [line, alt, metaseq, pk_error, long, variant]."""
+        """The per-alt records of the parsed lines, in line and ALT order."""
         recs = []
-        max_len = self._pk_generator.max_sequence_length()
         for li, p in enumerate(parsed):
             if len(p) != 2 or p[0] in ("skip", "error"):
                 continue
@@ -1100,98 +1128,73 @@ class VCFVariantLoader(object):
             for alt in v.alt_alleles:
                 if alt == ".":
                     continue
-                ref = v.ref_allele
-                metaseq = ":".join((_xstr(v.chromosome), _xstr(v.position), ref, alt))
+                metaseq = ":".join((_xstr(v.chromosome), _xstr(v.position), v.ref_allele, alt))
                 pk_err = None
                 if len(metaseq.split(":")) != 4:
                     # metaseqId.split(':') fails on every rung of the retry ladder
                     pk_err = ValueError("too many values to unpack (expected 4)")
-                recs.append([li, alt, metaseq, pk_err, len(ref) + len(alt) > max_len, v])
+                recs.append(_AltRecord(li, alt, metaseq, pk_err, v))
         return recs
 
-    def _small_prep(self, recs, res):
+    def _fill_keys(self, recs, pks, idx):
+        """Fills ``pks`` for the records ``idx`` from the PK generator (a key it
+        refuses becomes the record's ``pk_error``).  Returns ADSP's
+        is_duplicate(recordPK) per record (vcf_variant_loader.py:303-307), else None."""
+        if idx:
+            items = [(recs[i].metaseq, recs[i].variant.ref_snp_id) for i in idx]
+            for i, k in zip(idx, self._primary_keys(items)):
+                if isinstance(k, Exception):
+                    recs[i].pk_error = k
+                else:
+                    pks[i] = k
+        return self._existing.has_primary_keys(pks) if self.is_adsp() and self._existing is not None else None
+
+    def _small_prep(self, recs, res) -> _Prep:
         """K8's outputs as ``_gpu_prep`` returns them.  Keys K8 rendered are used
         as is; the others (long alleles: the VRS digest; ':' in an allele; ids
         without a canonical form) go through the PK generator, which raises where
         the reference raises."""
         from . import _native as N
-        n = len(recs)
-        pks: List[Optional[str]] = [None] * n
+        pks: List[Optional[str]] = [None] * len(recs)
         ks = res["key_state"]
-        items, idx = [], []
+        idx = []
         for i, r in enumerate(recs):
-            if r[3] is not None:
-                continue
-            if ks[i] == N.KEY_OK:
+            if r.pk_error is None and ks[i] == N.KEY_OK:
                 pks[i] = res["key"][i]
-            else:
-                items.append((r[2], r[5].ref_snp_id))
+            elif r.pk_error is None:
                 idx.append(i)
-        if items:
-            try:
-                for i, k in zip(idx, self._pk_generator.generate_primary_keys(items)):
-                    pks[i] = k
-            except ValueError:
-                for i, it in zip(idx, items):  # isolate the failing records
-                    try:
-                        pks[i] = self._pk_generator.generate_primary_keys([it])[0]
-                    except ValueError as err:
-                        recs[i][3] = err
-        self._match = None
-        self._adsp_dup = None
-        if self.is_adsp() and self._existing is not None:
-            self._adsp_dup = self._existing.has_primary_keys(pks)
+        adsp_dup = self._fill_keys(recs, pks, idx)
         disp = [d if st == 0 else None for d, st in zip(res["display"], res["disp_state"])]
-        return res["path"], pks, None, disp
+        return _Prep(res["path"], pks, None, disp, None, adsp_dup)
 
-    def _gpu_prep(self, recs, db, codes, dedup, keep_override=None):
+    def _gpu_prep(self, recs, db, codes, dedup, keep_override=None) -> _Prep:
         """K2 (+K3) and K5a on the device batch, then ltree text, primary keys
         and display-attribute JSON per record."""
         n = len(recs)
         pks: List[Optional[str]] = [None] * n
         if not n:
-            return [], pks, None, []
+            return _Prep([], pks, None, [])
         eng = self._engine
         d_end, d_code, d_status, _ = eng.record_prep(db, want_lcp=False)
-        if keep_override is not None:
-            keep = np.asarray(keep_override, dtype=np.uint8)
-        else:
-            d_keep = eng.pk_dedup(db, grouped=False) if dedup else None
-            keep = d_keep.cpu().numpy() if d_keep is not None else None
+        keep = None if keep_override is None else np.asarray(keep_override, dtype=np.uint8)
+        if keep is None and dedup:
+            keep = eng.pk_dedup(db, grouped=False).cpu().numpy()
         code = d_code.cpu().numpy().view(np.uint32)
         paths = eng.format_paths(np.asarray(codes, dtype=np.uint8), code)
         disp = _display_texts(eng, db, d_end)
-        self._match = None
+        match = None
         if self._existing is not None:  # --skipExisting (K6)
             m, k = self._existing.probe(db)
-            m, k = m.cpu().numpy(), k.cpu().numpy()
+            match, k = m.cpu().numpy(), k.cpu().numpy()
             for i in np.nonzero(k == 255)[0]:
                 # (a record whose key cannot be built raises before this check)
-                m[i] = self._existing.resolve_host(recs[i][2]) if recs[i][3] is None else -1
-            self._match = m
+                match[i] = self._existing.resolve_host(recs[i].metaseq) if recs[i].pk_error is None else -1
         # primary keys (short: text; long: K4 digests in one launch)
-        items, idx = [], []
-        for i, r in enumerate(recs):
-            if r[3] is None:
-                items.append((r[2], r[5].ref_snp_id))
-                idx.append(i)
-        try:
-            keys = self._pk_generator.generate_primary_keys(items)
-            for i, k in zip(idx, keys):
-                pks[i] = k
-        except ValueError:
-            for i, it in zip(idx, items):  # isolate the failing records
-                try:
-                    pks[i] = self._pk_generator.generate_primary_keys([it])[0]
-                except ValueError as err:
-                    recs[i][3] = err
-        # ADSP: is_duplicate(recordPK) against the exported keys (vcf_variant_loader.py:303-307)
-        self._adsp_dup = None
-        if self.is_adsp() and self._existing is not None:
-            self._adsp_dup = self._existing.has_primary_keys(pks)
-        return paths, pks, keep, disp
+        adsp_dup = self._fill_keys(recs, pks, [i for i, r in enumerate(recs) if r.pk_error is None])
+        return _Prep(paths, pks, keep, disp, match, adsp_dup)
 
-    def _emit(self, parsed, recs, paths, pks, keep, disp, errors):
+    def _emit(self, parsed, recs, prep: _Prep, errors):
+        paths, pks, keep, disp, match, adsp_dup = prep
         out = []
         ri = 0
         for li, p in enumerate(parsed):
@@ -1213,22 +1216,21 @@ class VCFVariantLoader(object):
                     self.logger.warning("Skipping variant " + v.id + "; no alt allele (alt = .)")
                     self.increment_counter("skipped")
                     continue
-                r = recs[ri]
-                i = ri
+                i, r = ri, recs[ri]
                 ri += 1
                 # same order of failure as vcf_variant_loader.py:282-328: key, bin, FREQ
-                if r[3] is not None:
-                    failed = r[3] if isinstance(r[3], Exception) else ValueError(str(r[3]))
+                if r.pk_error is not None:
+                    failed = r.pk_error
                     break
-                if self._match is not None and self._match[i] >= 0:  # vcf_variant_loader.py:285-291
-                    mapping += self._existing.payload(int(self._match[i]))
+                if match is not None and match[i] >= 0:  # vcf_variant_loader.py:285-291
+                    mapping += self._existing.payload(int(match[i]))
                     self.increment_counter("skipped")
                     continue
                 if self.is_adsp():  # vcf_variant_loader.py:303-307
-                    if self._adsp_dup is None:  # no validator: the reference's None.exists(...)
+                    if adsp_dup is None:  # no validator: the reference's None.exists(...)
                         failed = AttributeError("'NoneType' object has no attribute 'exists'")
                         break
-                    if self._adsp_dup[i]:
+                    if adsp_dup[i]:
                         self._update_buffer.append((pks[i], "chr" + _xstr(v.chromosome)))
                         self.increment_counter("update")
                         continue
@@ -1249,7 +1251,7 @@ class VCFVariantLoader(object):
                     self.increment_counter("duplicates")
                 else:
                     self.add_copy_str("#".join([
-                        "chr" + _xstr(v.chromosome), pk, _xstr(v.position), r[2], path,
+                        "chr" + _xstr(v.chromosome), pk, _xstr(v.position), r.metaseq, path,
                         _xstr(self._alg_invocation_id), _xstr(v.ref_snp_id, nullStr="NULL"),
                         _xstr(v.is_multi_allelic, falseAsNull=True, nullStr="NULL"), disp[i], freq]
                         + (["True"] if self.is_adsp() else [])))  # is_adsp_variant (:336-337)
@@ -1259,7 +1261,8 @@ class VCFVariantLoader(object):
                 if errors == "raise":
                     raise failed
                 out.append(failed)
-                ri = _next_line_start(recs, ri, li)  # past this line's remaining alts
+                while ri < len(recs) and recs[ri].line == li:  # past this line's remaining alts
+                    ri += 1
                 continue
             out.append({v.id: mapping})
         return out
@@ -1274,10 +1277,7 @@ class _LineVariant:
         self.line, self.id, self.loader = line, vid, loader
 
     def resolve(self):
-        ld = self.loader
-        e = VcfEntryParser(self.line, ld._vcf_header_fields)
-        e.update_chromosome(ld._chromosome_map)
-        return e.get_variant(dbSNP=ld.is_dbsnp(), namespace=True)
+        return self.loader._host_variant(self.line)[1]
 
 
 class _LazyEntry:
@@ -1321,12 +1321,6 @@ def _select(b, idx):
     return RecordBatch(chrom=b.chrom[idx], pos=b.pos[idx], allele_off=b.allele_off[idx],
                        ref_len=b.ref_len[idx], alt_len=b.alt_len[idx], heap=b.heap,
                        ext_id=b.ext_id[idx])
-
-
-def _next_line_start(recs, ri, li):
-    while ri < len(recs) and recs[ri][0] == li:
-        ri += 1
-    return ri
 
 
 def _freq_str(entry, alt):

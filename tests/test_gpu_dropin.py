@@ -278,6 +278,83 @@ def test_loader_text_path_comments_and_edge_lines(loader):
     assert host == outs
 
 
+def test_text_paths_agree_on_host_flagged_lines(loader, engine):
+    """Lines K0 flags for the host (each VCF_HOST_FLAGS bit at least once) through
+    parse_vcf_text and load_vcf_text against the per-line path: results, COPY rows,
+    .mapping text and counters with errors='record'; the exception, the line it
+    stops at and the rows before it with errors='raise'."""
+    from annotatedvdb_amd.engine import (VCF_BAD_POS, VCF_CHROM_HOST, VCF_COMMENT, VCF_EXT_HOST,
+                                         VCF_FEW_FIELDS, VCF_HOST_FLAGS, VCF_ID_HOST)
+    from annotatedvdb_amd.loaders import _data_lines, _mapping_text
+    text = "\n".join(["##fileformat=VCFv4.2",
+                      "#CHROM\tPOS\tID\tREF\tALT\tQUAL\tFILTER\tINFO",
+                      "1\t10177\trs367896724\tA\tAC\t.\t.\tRS=367896724",
+                      "+1\t2000\t.\tA\tG,.,T\t.\t.\tRS=abc",       # CHROM and refSNP from the host; 2 records + '.'
+                      "2\t500\t.\tG\tT\t.\t.\tRS=5",               # unflagged, between flagged lines
+                      "3\t1e3\trs9\tC\tG,GA\t.\t.\t.",             # POS from the host
+                      "# a comment in the middle",
+                      "6\t800\t.\tA\tC\t.\t.\tRS=0",               # refSNP from the host
+                      "5\t700\t12345\tT\tC\t.\t.\tRS=7",           # all-digit ID: the host parse raises
+                      "chrUn_KI270302v1\t100\t.\tC\tT\t.\t.\t.",   # CHROM from the host: no bin
+                      "7\t100\t.\tA",                              # fewer than 8 fields: the host parse raises
+                      "8\t900\trs77\tG\tA\t.\t.\tRS=77",
+                      "9\t1e2\t.\tG\tA,.\t.\t.\t."]).encode()      # no trailing newline
+    flags = engine.vcf_tokenize(text).lines_host()["flags"]
+    assert len(flags) == 13
+    for bit in (VCF_BAD_POS, VCF_EXT_HOST, VCF_CHROM_HOST, VCF_ID_HOST):
+        assert (flags & bit).any(), hex(bit)
+    assert [bool(f & VCF_HOST_FLAGS) for f in flags] == [False, False, False, True, False, True, False, True, True,
+                                                         True, False, False, True]
+    assert flags[3] & VCF_CHROM_HOST and flags[3] & VCF_EXT_HOST and flags[6] & VCF_COMMENT
+    assert flags[10] & VCF_FEW_FIELDS
+    lines = _data_lines(text)
+    assert len(lines) == 10
+
+    def run(fn, errors):
+        loader.reset_copy_buffer()
+        loader._initialize_counters()
+        err = out = None
+        try:
+            out = fn(errors)
+        except Exception as e:  # noqa: BLE001
+            err = e
+        return out, err, loader.copy_buffer().getvalue(), {k: loader.get_count(k) for k in ("line", "variant", "skipped")}
+
+    def per_line(errors):  # pinned to the reference by the golden tests: the expectation
+        return loader.parse_variants(lines, errors=errors)
+
+    def text_path(errors):
+        return loader.parse_vcf_text(text, errors=errors)
+
+    def load_path(errors):
+        return loader.load_vcf_text(text, errors=errors)
+
+    out_a, err, copy_a, ctr_a = run(per_line, "record")
+    assert err is None and len(out_a) == 10
+    assert [type(o).__name__ for o in out_a] == ["dict", "dict", "dict", "dict", "dict", "AttributeError", "TypeError",
+                                                 "IndexError", "dict", "dict"]
+    assert len(out_a[1]["1:2000:A:G,.,T"]) == 2 and out_a[1]["1:2000:A:G,.,T"][1]["primary_key"] == "1:2000:A:T:rsabc"
+    assert ctr_a == {"line": 10, "variant": 9, "skipped": 2} and copy_a.count("\n") == 9
+    out_b, err, copy_b, ctr_b = run(text_path, "record")
+    assert err is None
+    assert [o if isinstance(o, dict) else (type(o), str(o)) for o in out_b] == \
+        [o if isinstance(o, dict) else (type(o), str(o)) for o in out_a]
+    assert (copy_b, ctr_b) == (copy_a, ctr_a)
+    map_c, err, copy_c, ctr_c = run(load_path, "record")
+    assert err is None
+    assert map_c == "".join(_mapping_text(o) for o in out_a if isinstance(o, dict))
+    assert (copy_c, ctr_c) == (copy_a, ctr_a)
+
+    # errors='raise': all three stop at the all-digit ID, with the five lines before it emitted
+    _, err_a, copy_a, ctr_a = run(per_line, "raise")
+    assert type(err_a) is AttributeError and ctr_a["line"] == 6 and copy_a.count("\n") == 7
+    for fn in (text_path, load_path):
+        _, err, copy, ctr = run(fn, "raise")
+        assert (type(err), str(err)) == (type(err_a), str(err_a))
+        assert (copy, ctr) == (copy_a, ctr_a)
+    assert err.avdb_partial_mapping == "".join(_mapping_text(o) for o in out_a[:5])
+
+
 def test_variant_annotator_display_attributes_matches_reference():
     from annotatedvdb_amd.variant_annotator import VariantAnnotator
     rows = read_tsv("display_attrs.tsv.gz")[:200]
