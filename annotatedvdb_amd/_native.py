@@ -69,6 +69,12 @@ EXIST_ALL_CONTIGS = 0xFFFFFFFF
 EXIST_COUNTS = ("rows", "skipped", "frag_host", "noncanon", "lone_cr", "key_bytes", "pk_bytes",
                 "frag_bytes")  # AVDB_EXIST_COUNT_*, by slot
 EXIST_N_COUNTS = len(EXIST_COUNTS)
+CADDUPD_ROW_HOST, CADDUPD_BAD = 1, 2  # AVDB_CADDUPD_* row flags
+CADDUPD_SKIP_EXISTING = 1
+CADDUPD_CHROM_MAX, CADDUPD_SCORE_MAX = 64, 24
+CADDUPD_COUNTS = ("rows", "skipped_lines", "skipped", "snv", "indel", "not_matched", "host_rows", "bad", "lone_cr",
+                  "out_bytes")  # AVDB_CADDUPD_COUNT_*, by slot
+CADDUPD_N_COUNTS = len(CADDUPD_COUNTS)
 MAX_ALG_ID = 64
 BGZF_STATUS = ("OK", "bad header", "input overrun", "bad block type", "bad stored length", "bad code lengths",
                "bad symbol", "distance before block start", "output longer than ISIZE", "output shorter than ISIZE",
@@ -143,6 +149,8 @@ EXPORTED_SYMBOLS = [
     "avdb_bgzf_index_host", "avdb_bgzf_inflate", "avdb_bgzf_inflate_host",
     "avdb_existing_workspace_size", "avdb_existing_size", "avdb_existing_write",
     "avdb_existing_size_host", "avdb_existing_write_host",
+    "avdb_cadd_update_workspace_size", "avdb_cadd_update_size", "avdb_cadd_update_write",
+    "avdb_cadd_update_size_host", "avdb_cadd_update_write_host", "avdb_cadd_score_text_host",
 ]
 
 
@@ -279,6 +287,13 @@ def _sig(lib):
     f.avdb_existing_size.argtypes = f.avdb_existing_size_host.argtypes + [P, SZ, P]
     f.avdb_existing_write_host.argtypes = [P, P, SZ, SZ, SZ, P, P, P, P, P, P, SZ, P, P, SZ, P, P, SZ, P, P]
     f.avdb_existing_write.argtypes = f.avdb_existing_write_host.argtypes + [P, SZ, P]
+    T = ctypes.POINTER(CaddTableView)
+    f.avdb_cadd_update_workspace_size.argtypes = [SZ, SZ, ctypes.POINTER(SZ)]
+    f.avdb_cadd_update_size_host.argtypes = [P, P, SZ, SZ, T, T, ctypes.c_char_p, SZ, U32, U32, P, P, P, P, P, P, P]
+    f.avdb_cadd_update_size.argtypes = f.avdb_cadd_update_size_host.argtypes + [P, SZ, P]
+    f.avdb_cadd_update_write_host.argtypes = [P, P, SZ, SZ, SZ, T, T, ctypes.c_char_p, SZ, P, P, P, P, P, P, P, SZ, P, P]
+    f.avdb_cadd_update_write.argtypes = f.avdb_cadd_update_write_host.argtypes + [P, SZ, P]
+    f.avdb_cadd_score_text_host.argtypes = [P, SZ, P, SZ, ctypes.POINTER(SZ)]
     for name in EXPORTED_SYMBOLS:
         if name not in ("avdb_last_error",):
             getattr(f, name).restype = I32

@@ -24,7 +24,16 @@ of a variant's primary key by metaseq id (``__get_variant_primary_key`` →
 ``is_duplicate``; here the records carry ``record_primary_key``, which is what
 ``SELECT_SQL`` of ``load_cadd_scores.py:29`` returns) and the ``UPDATE`` itself
 (``update_variants``: ``execute_values`` over :meth:`CADDUpdater.update_buffer`).
-``json.dumps`` of the two scores per matched record also stays on the host.
+
+A whole export of the variants (the rows ``SELECT_SQL`` returns, as ``COPY ... TO
+STDOUT`` writes them) goes through :meth:`CADDUpdater.buffer_export` instead of
+``buffer_variants``: K13 (``avdb_cadd_update_size`` / ``avdb_cadd_update_write``)
+splits the lines, joins them against the tables and writes the update rows as text on
+the GPU, the JSON of the two scores included: for every score text the table build
+parses, ``json.dumps(float(text))`` is a rewrite of the text's own digits.  Only rows
+the device does not decide (a contig without a code, a position that is not plain
+digits, a table score left to ``float()``) are rendered by ``buffer_variants``' host
+code.  ``annotatedvdb_amd.load_cadd_scores`` is the command-line driver over it.
 """
 
 from __future__ import annotations
@@ -178,6 +187,9 @@ class CADDUpdater(object):
         self._counters = {"line": 0, "variant": 0, "skipped": 0, "duplicates": 0, "update": 0,
                           "snv": 0, "indel": 0, "not_matched": 0}
         self._update_buffer: List[tuple] = []
+        # rows buffer_export appended, not yet split into tuples: (index in _update_buffer they
+        # stand before, number of rows, their text)
+        self._export_rows: List[tuple] = []
 
     # ---- the reference's surface -----------------------------------------------
     def set_chromosome(self, chrm):
@@ -199,10 +211,28 @@ class CADDUpdater(object):
         return self.get_count("update") + self.get_count("not_matched") + self.get_count("skipped")
 
     def update_buffer(self, sizeOnly=False):
-        return len(self._update_buffer) if sizeOnly else self._update_buffer
+        """The buffered ``(pk, chrom, json)`` tuples, rows from :meth:`buffer_export`
+        included (split into tuples at the first call that asks for them)."""
+        if sizeOnly:
+            return len(self._update_buffer) + sum(n for _, n, _ in self._export_rows)
+        for at, _, text in reversed(self._export_rows):
+            rows = text.decode("utf-8", "surrogateescape").split("\n")[:-1]
+            self._update_buffer[at:at] = [tuple(r.split("\t")) for r in rows]
+        self._export_rows = []
+        return self._update_buffer
+
+    def update_text(self) -> bytes:
+        """The buffered rows as text, ``pk<TAB>chrom<TAB>json<LF>`` each, in buffer order."""
+        parts, done = [], 0
+        for at, _, text in self._export_rows + [(len(self._update_buffer), 0, b"")]:
+            parts += [("\t".join(t) + "\n").encode("utf-8", "surrogateescape") for t in self._update_buffer[done:at]]
+            parts.append(text)
+            done = at
+        return b"".join(parts)
 
     def reset_update_buffer(self):
         self._update_buffer = []
+        self._export_rows = []
 
     def snv(self):
         return self._snv
@@ -283,3 +313,25 @@ class CADDUpdater(object):
             c = chrm if chrm is not None else "chr" + str(pk.split(":")[0])
             self._update_buffer.append((pk, c, json.dumps(evidence)))
         return len(todo)
+
+    def buffer_export(self, path_or_text, skip_existing: bool = True, contigs=None):
+        """:meth:`buffer_variants` over a whole export (K13,
+        :meth:`Engine.cadd_update_rows`): ``record_primary_key<TAB>metaseq_id<TAB>cadd_scores``
+        lines, ``cadd_scores`` NULL as ``\\N``, empty or absent, given as a path (plain,
+        gzip or bgzip) or as text (bytes, numpy ``uint8`` or a ``uint8`` tensor).
+        ``contigs``: keep only the rows whose metaseq id carries one of these labels, so
+        that one whole-table export serves every per-chromosome pass.  Moves ``snv``,
+        ``indel``, ``update``, ``not_matched`` and ``skipped`` and appends the rows as
+        ``buffer_variants`` would for the same records; returns their number."""
+        if isinstance(path_or_text, str):
+            from . import bgzf
+            path_or_text = bgzf.read_whole(path_or_text, self._engine)
+        rows = self._engine.cadd_update_rows(path_or_text, self._snv, self._indel, chromosome=self.__chromosome,
+                                             skip_existing=skip_existing, contigs=contigs)
+        c = rows.counts
+        for name, k in (("snv", c["snv"]), ("indel", c["indel"]), ("update", c["snv"] + c["indel"]),
+                        ("not_matched", c["not_matched"]), ("skipped", c["skipped"])):
+            self._counters[name] += k
+        if rows.n:
+            self._export_rows.append((len(self._update_buffer), rows.n, rows.text.cpu().numpy().tobytes()))
+        return rows.n

@@ -189,30 +189,13 @@ extern "C" int avdb_cadd_table_build(avdb_ctx* ctx, const uint8_t* text, size_t 
   return AVDB_OK;
 }
 
-// a caller's table as the join reads it; false: a struct this library cannot read
-static bool cadd_view(const avdb_cadd_table* t, View* v, const char** err) {
-  *v = View{};
-  if (!t) return true;
-  if (t->struct_size != sizeof(avdb_cadd_table)) { *err = "avdb_cadd_table.struct_size does not match this library"; return false; }
-  if (t->n_rows == 0) return true;
-  if (t->n_rows >= 0x7FFFFFFFull) { *err = "table of 2^31 rows or more"; return false; }
-  if (!t->text || !t->chrom || !t->pos || !t->ref_off || !t->ref_len || !t->alt_off || !t->alt_len || !t->raw ||
-      !t->phred || !t->flags || !t->first_row || !t->end_row) {
-    *err = "null table column";
-    return false;
-  }
-  *v = View{t->n_rows, t->text,  t->chrom, t->pos,   t->ref_off,   t->ref_len, t->alt_off,
-            t->alt_len, t->raw, t->phred, t->flags, t->first_row, t->end_row};
-  return true;
-}
-
 static const char* match_args_error(const void* ctx, const avdb_cadd_table* snv, const avdb_cadd_table* indel, View* vs,
                                     View* vi, const uint8_t* chrom, const uint32_t* pos, const uint64_t* allele_off,
                                     const uint32_t* ref_len, const uint32_t* alt_len, const uint8_t* heap, size_t n,
                                     const int32_t* row, const uint8_t* kind, const double* raw, const double* phred) {
   if (!ctx) return "null context";
   const char* err = nullptr;
-  if (!cadd_view(snv, vs, &err) || !cadd_view(indel, vi, &err)) return err;
+  if (!cadd::table_view(snv, vs, &err) || !cadd::table_view(indel, vi, &err)) return err;
   if (n == 0) return nullptr;
   if (!chrom || !pos || !allele_off || !ref_len || !alt_len || !heap) return "null record array";
   if (!row || !kind || !raw || !phred) return "null output array";

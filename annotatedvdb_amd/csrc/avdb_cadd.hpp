@@ -238,6 +238,23 @@ AVDB_HD int64_t match_rows(const View& t, uint32_t c, uint32_t pos, const uint8_
   return -1;
 }
 
+// a caller's table as the join reads it; false: a struct this library cannot read
+inline bool table_view(const avdb_cadd_table* t, View* v, const char** err) {
+  *v = View{};
+  if (!t) return true;
+  if (t->struct_size != sizeof(avdb_cadd_table)) { *err = "avdb_cadd_table.struct_size does not match this library"; return false; }
+  if (t->n_rows == 0) return true;
+  if (t->n_rows >= 0x7FFFFFFFull) { *err = "table of 2^31 rows or more"; return false; }
+  if (!t->text || !t->chrom || !t->pos || !t->ref_off || !t->ref_len || !t->alt_off || !t->alt_len || !t->raw ||
+      !t->phred || !t->flags || !t->first_row || !t->end_row) {
+    *err = "null table column";
+    return false;
+  }
+  *v = View{t->n_rows, t->text,  t->chrom, t->pos,   t->ref_off,   t->ref_len, t->alt_off,
+            t->alt_len, t->raw, t->phred, t->flags, t->first_row, t->end_row};
+  return true;
+}
+
 // one record: *row and the kind; raw / phred written only for a matched record
 AVDB_HD uint32_t match_record(const View& snv, const View& indel, uint32_t c, uint32_t pos, const uint8_t* heap,
                               uint64_t heap_bytes, uint64_t off, uint32_t rl, uint32_t al, int32_t* row, double* raw,

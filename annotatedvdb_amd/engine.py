@@ -116,6 +116,22 @@ class ExistingColumns:
     counts: Dict[str, int]
 
 
+@dataclass
+class CaddUpdateRows:
+    """What K13 makes of an export of ``AnnotatedVDB.Variant``
+    (:meth:`Engine.cadd_update_rows`): ``text`` holds the ``n`` update rows
+    (``pk<TAB>chrom<TAB>json<LF>``, row ``i`` at ``row_off[i] .. row_off[i + 1]``),
+    ``kind`` their ``N.CADD_NONE`` / ``CADD_SNV`` / ``CADD_INDEL``, ``flags`` their
+    ``N.CADDUPD_*`` flags, ``counts`` the pass's counts by name (``N.CADDUPD_COUNTS``;
+    ``snv`` / ``indel`` / ``not_matched`` include the rows resolved on the host)."""
+    n: int
+    text: torch.Tensor
+    row_off: torch.Tensor
+    kind: torch.Tensor
+    flags: torch.Tensor
+    counts: Dict[str, int]
+
+
 def existing_contig_mask(contigs) -> int:
     """K12's contig mask: ``None`` keeps every row; otherwise one bit per label of
     ``contigs`` (``CHROM_NAMES`` index; bit 31 for any other label)."""
@@ -1391,6 +1407,115 @@ class Engine:
             raise N.NativeError("avdb_existing_write" + suffix, N.AVDB_ERANGE,
                                 f"blob totals {tot[:3]} do not fit the sizes the size pass gave")
         return ExistingColumns(n, keys, key_off, pks, pk_off, frag, frag_off, flags[:n], cnt)
+
+    # -- K13: CADD update rows from an export -------------------------------------
+    def cadd_update_rows(self, text, snv, indel, chromosome=None, skip_existing: bool = True,
+                         contigs=None) -> "CaddUpdateRows":
+        """K13: a slab of an export in the reference's ``SELECT_SQL`` column order
+        (``record_primary_key<TAB>metaseq_id<TAB>cadd_scores[<TAB>...]`` lines; bytes,
+        numpy ``uint8`` or a ``uint8`` tensor) joined against the two CADD tables
+        (:class:`~annotatedvdb_amd.cadd.CaddTable` or :class:`CaddColumns`, either may be
+        ``None``) -> :class:`CaddUpdateRows` on this engine's device: the text of the
+        tuples ``CADDUpdater.buffer_variants`` would append for the same records, in
+        file order.  ``chromosome``: what ``set_chromosome`` takes (``None``: each row's
+        ``chr`` + the label of its primary key); ``skip_existing``: records whose
+        ``cadd_scores`` is not NULL (``\\N``, empty or absent) are counted ``skipped``;
+        ``contigs``: labels of the metaseq ids whose rows to keep (``None``: all), as
+        for :meth:`existing_table_build`.  Three syncs: the line count, the size pass's
+        counts (the output is allocated from them), the end.  Rows the device leaves to
+        the host (``host_rows``: a contig without a code, a position that is not plain
+        digits, a table score the device does not parse) are rendered here with
+        ``buffer_variants`` itself and copied into their spans after the write pass.
+        On a host-only engine the library's host entries run the same per-line code."""
+        from .cadd import CADDUpdater, CaddTable
+        tabs = [t if t is None or isinstance(t, CaddTable) else CaddTable(t, self) for t in (snv, indel)]
+        for t in tabs:
+            if t is not None and t.cols.text.device != self.device:
+                raise ValueError("CADD table lives on another device than this engine")
+        views = [t.cols.view() if t is not None else None for t in tabs]
+        vp = [ctypes.byref(v) if v is not None else None for v in views]
+        chrom = None
+        if chromosome is not None:
+            label = str(chromosome).replace("chr", "")  # set_chromosome, then buffer_update_values' prefix
+            chrom = (label if "chr" in label else "chr" + label).encode("utf-8")
+            if not 0 < len(chrom) <= N.CADDUPD_CHROM_MAX:
+                raise ValueError(f"chromosome text of {len(chrom)} bytes (1 .. {N.CADDUPD_CHROM_MAX} taken)")
+        shared = (*vp, chrom, len(chrom) if chrom else 0)
+        text = self._as_text(text)
+        nb = text.numel()
+        n_lines = self._count_lines(text)
+        m = max(1, n_lines)
+        row_start = self.empty(m, torch.int64)
+        pk_len, out_len = self.empty(m, torch.int32), self.empty(m, torch.int32)
+        match = self.empty(m, torch.int32)
+        kind, flags = self.empty(m, torch.uint8), self.empty(m, torch.uint8)
+        counts = self.empty(N.CADDUPD_N_COUNTS, torch.int64)
+        tp = text if nb else None
+        if self.host_only:
+            run, suffix, tail = self._call, "_host", ()
+        else:
+            ws = self.scratch("cadd_update", N.size("avdb_cadd_update_workspace_size", nb, n_lines))
+            run, suffix, tail = self._launch, "", (ws, ws.numel())
+        run("avdb_cadd_update_size" + suffix, tp, nb, n_lines, *shared, existing_contig_mask(contigs),
+            N.CADDUPD_SKIP_EXISTING if skip_existing else 0, row_start, pk_len, kind, match, out_len, flags, counts,
+            *tail)
+        cnt = dict(zip(N.CADDUPD_COUNTS, (int(x) for x in counts.cpu().numpy().astype(np.uint64))))
+        if cnt["lone_cr"]:
+            raise ValueError(f"{cnt['lone_cr']} carriage return(s) in the export that no newline follows: Python's "
+                             "text mode ends a line there and the device pass does not; feed this export to "
+                             "CADDUpdater.buffer_variants record by record")
+        n = cnt["rows"]
+        if cnt["bad"]:
+            first = int(row_start[:n][(flags[:n] & N.CADDUPD_BAD) != 0][0])
+            line = int((text[:first] == 10).sum()) + 1
+            raise ValueError(f"line {line} of the export: the metaseq id does not have the four parts "
+                             f"chrom:pos:ref:alt ({cnt['bad']} such line(s))")
+        out_bytes = cnt["out_bytes"]
+        host_rows = rendered = None
+        if cnt["host_rows"]:
+            host_rows = torch.nonzero(flags[:n] & N.CADDUPD_ROW_HOST).flatten()
+            start = row_start[host_rows]
+            nxt = torch.where(host_rows + 1 < n, row_start[torch.clamp(host_rows + 1, max=max(n - 1, 0))],
+                              torch.full_like(start, nb))
+            span = nxt - start  # the row's line, and the skipped lines behind it
+            raw = text[self._spans(start, span)].cpu().numpy().tobytes()
+            recs, at = [], 0
+            for s in span.tolist():
+                f = raw[at:at + s].split(b"\n", 1)[0]
+                at += s
+                f = (f[:-1] if f.endswith(b"\r") and len(f) < s else f).split(b"\t")
+                recs.append({"record_primary_key": f[0].decode("utf-8", "surrogateescape"),
+                             "metaseq_id": f[1].decode("utf-8", "surrogateescape")})
+            u = CADDUpdater(tabs[0], tabs[1], self)
+            if chromosome is not None:
+                u.set_chromosome(chromosome)
+            u.buffer_variants(recs, skip_existing=False)
+            out = [("\t".join(t) + "\n").encode("utf-8", "surrogateescape") for t in u.update_buffer()]
+            kinds = []
+            for rec, t in zip(recs, u.update_buffer()):
+                _, _, r, a = rec["metaseq_id"].split(":")
+                kinds.append(N.CADD_NONE if t[2] == "{}" else N.CADD_INDEL if len(r) > 1 or len(a) > 1 else N.CADD_SNV)
+            for name in ("snv", "indel", "not_matched"):
+                cnt[name] += u.get_count(name)
+            new_len = torch.tensor([len(x) for x in out], dtype=torch.int64)
+            out_bytes += int(new_len.sum())
+            out_len[host_rows] = new_len.to(torch.int32).to(self.device)
+            kind[host_rows] = torch.tensor(kinds, dtype=torch.uint8).to(self.device)
+            rendered = (torch.from_numpy(np.frombuffer(b"".join(out), dtype=np.uint8).copy()).to(self.device),
+                        new_len.to(self.device))
+        cnt["out_bytes"] = out_bytes
+        out_text = self.empty(max(1, out_bytes), torch.uint8)
+        row_off = self.empty(n + 1, torch.int64)
+        totals = self.empty(2, torch.int64)
+        run("avdb_cadd_update_write" + suffix, tp, nb, n_lines, n, *shared, row_start, pk_len, kind, match, out_len,
+            flags, out_text, out_bytes, row_off, totals, *tail)
+        if rendered is not None:
+            out_text[self._spans(row_off[host_rows], rendered[1])] = rendered[0]
+        tot = totals.cpu().tolist()
+        if tot[1] or tot[0] != out_bytes:
+            raise N.NativeError("avdb_cadd_update_write" + suffix, N.AVDB_ERANGE,
+                                f"rows of {tot[0]} bytes do not fit the {out_bytes} the size pass gave")
+        return CaddUpdateRows(n, out_text[:out_bytes], row_off, kind[:n], flags[:n], cnt)
 
     # -- K10: CADD table and allele join ---------------------------------------
     def new_cadd_counters(self) -> torch.Tensor:

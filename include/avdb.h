@@ -919,6 +919,96 @@ int avdb_existing_write_host(const avdb_ctx* ctx, const uint8_t* text, size_t te
                              size_t keys_cap, uint64_t* key_off, uint8_t* pks, size_t pks_cap, uint64_t* pk_off,
                              uint8_t* frag, size_t frag_cap, uint64_t* frag_off, uint64_t* totals);
 
+/* ---- K13: CADD update rows from a variant export --------------------------------
+ * Replaces the per-record host code around the K10 join in the CADD pass
+ * (Load/bin/load_cadd_scores.py:109-120, cadd_updater.py:121-130,187-221): `text` is a
+ * slab of an export in the column order of the reference's SELECT_SQL,
+ * `record_primary_key<TAB>metaseq_id<TAB>cadd_scores[<TAB>...]` lines separated by '\n'
+ * (n_lines as for K0, K10a and K12), and the output is the text of the update tuples,
+ * one `pk<TAB>chrom<TAB>json<LF>` row per record that is not skipped.
+ * Row rule: one trailing '\r' before the '\n' is stripped; an empty line, a line with
+ * fewer than two fields and a line whose first field is exactly `record_primary_key`
+ * are no row (counts[AVDB_CADDUPD_COUNT_SKIPPED_LINES]); fields after the third are
+ * ignored.  A '\r' no '\n' follows is counted (AVDB_CADDUPD_COUNT_LONE_CR) and the
+ * caller decides.  contig_mask: as for K12, over the label of the metaseq id (the text
+ * before its first ':'); a line whose bit is clear is skipped as if it were absent.
+ * With AVDB_CADDUPD_SKIP_EXISTING a line whose third field is present and neither empty
+ * nor `\N` is counted in AVDB_CADDUPD_COUNT_SKIPPED and is no row.  Every other line is
+ * a row, in file order:
+ *   - a metaseq id without exactly three ':' is flagged AVDB_CADDUPD_BAD (no output);
+ *   - label: 1..22, X, Y, M, and MT as M; position: 1 to 10 decimal digits below 2^32;
+ *     the indel table when len(ref) > 1 or len(alt) > 1, else the SNV table; the K10
+ *     join (avdb_cadd_match's row test) with the alleles read in the export text;
+ *   - pk is copied verbatim; chrom is the caller's `chrom` text when chrom_len > 0
+ *     (at most AVDB_CADDUPD_CHROM_MAX bytes, host memory), else `chr` + the bytes of
+ *     pk before its first ':'; json is `{}` when no row matches, else
+ *     `{"CADD_raw_score": R, "CADD_phred": P}` with R and P rewritten from the table's
+ *     own score text into what Python's json.dumps(float(text)) gives (exact for every
+ *     text K10a parses: the digits are kept, only zeros, the point and the exponent
+ *     move);
+ *   - a label outside the 25, a position that is not plain digits below 2^32, or a
+ *     matched table row flagged AVDB_CADD_ROW_SCORE_HOST: AVDB_CADDUPD_ROW_HOST, output
+ *     length 0; the caller renders the row, stores its length in out_len[row] before
+ *     the write pass, and overwrites the row's span (filled with spaces) after it.
+ *   1. avdb_cadd_update_size: per row (n_lines entries allocated, rows written)
+ *      row_start (u64: the offset of the row's line in the slab), pk_len, kind
+ *      (AVDB_CADD_NONE / _SNV / _INDEL), match (the table row, -1: none), out_len and
+ *      row_flags; counts (AVDB_CADDUPD_N_COUNTS x u64, set by the call).  snv / indel /
+ *      not_matched count the rows the device decided; out_bytes sums out_len.
+ *   2. avdb_cadd_update_write (n_rows = counts[AVDB_CADDUPD_COUNT_ROWS]; the same text,
+ *      tables, chrom and arrays): scans out_len into row_off (n_rows + 1 entries) and
+ *      writes the rows to out (8-byte aligned, out_cap bytes).  totals (2 x u64): the
+ *      bytes of all rows, and 1 when they exceed out_cap.  Nothing outside [0, total)
+ *      is written, and nothing at all when out_cap is too small: the host entry returns
+ *      AVDB_ERANGE then; the device entry, which does not wait for its own scan, returns
+ *      AVDB_OK and leaves totals[1] != 0 for the caller to read after the stream.
+ * avdb_cadd_score_text_host: the rewrite of one score text alone (out: cap >=
+ * AVDB_CADDUPD_SCORE_MAX bytes); returns 1 and *len, or 0 for a text K10a leaves to the
+ * host (AVDB_CADD_ROW_SCORE_HOST).
+ * Workspace: avdb_cadd_update_workspace_size bytes, 256-byte aligned; the device entries
+ * allocate nothing per call.  The _host entries run the same per-line code on host
+ * pointers, on an avdb_ctx_create(-1, ...) context. */
+#define AVDB_CADDUPD_ROW_HOST 0x01u
+#define AVDB_CADDUPD_BAD 0x02u
+#define AVDB_CADDUPD_SKIP_EXISTING 0x01u  /* avdb_cadd_update_size's flags */
+#define AVDB_CADDUPD_CHROM_MAX 64
+#define AVDB_CADDUPD_SCORE_MAX 24
+#define AVDB_CADDUPD_COUNT_ROWS 0
+#define AVDB_CADDUPD_COUNT_SKIPPED_LINES 1  /* lines that are no row and no skipped record */
+#define AVDB_CADDUPD_COUNT_SKIPPED 2        /* records annotated already */
+#define AVDB_CADDUPD_COUNT_SNV 3
+#define AVDB_CADDUPD_COUNT_INDEL 4
+#define AVDB_CADDUPD_COUNT_NOT_MATCHED 5
+#define AVDB_CADDUPD_COUNT_HOST_ROWS 6
+#define AVDB_CADDUPD_COUNT_BAD 7
+#define AVDB_CADDUPD_COUNT_LONE_CR 8
+#define AVDB_CADDUPD_COUNT_OUT_BYTES 9
+#define AVDB_CADDUPD_N_COUNTS 10
+int avdb_cadd_update_workspace_size(size_t text_bytes, size_t n_lines, size_t* bytes);
+int avdb_cadd_update_size(avdb_ctx* ctx, const uint8_t* text, size_t text_bytes, size_t n_lines,
+                          const avdb_cadd_table* snv, const avdb_cadd_table* indel, const char* chrom, size_t chrom_len,
+                          uint32_t contig_mask, uint32_t flags, uint64_t* row_start, uint32_t* pk_len, uint8_t* kind,
+                          int32_t* match, uint32_t* out_len, uint8_t* row_flags, uint64_t* counts, void* workspace,
+                          size_t workspace_bytes, void* stream);
+int avdb_cadd_update_write(avdb_ctx* ctx, const uint8_t* text, size_t text_bytes, size_t n_lines, size_t n_rows,
+                           const avdb_cadd_table* snv, const avdb_cadd_table* indel, const char* chrom,
+                           size_t chrom_len, const uint64_t* row_start, const uint32_t* pk_len, const uint8_t* kind,
+                           const int32_t* match, const uint32_t* out_len, const uint8_t* row_flags, uint8_t* out,
+                           size_t out_cap, uint64_t* row_off, uint64_t* totals, void* workspace,
+                           size_t workspace_bytes, void* stream);
+int avdb_cadd_update_size_host(const avdb_ctx* ctx, const uint8_t* text, size_t text_bytes, size_t n_lines,
+                               const avdb_cadd_table* snv, const avdb_cadd_table* indel, const char* chrom,
+                               size_t chrom_len, uint32_t contig_mask, uint32_t flags, uint64_t* row_start,
+                               uint32_t* pk_len, uint8_t* kind, int32_t* match, uint32_t* out_len, uint8_t* row_flags,
+                               uint64_t* counts);
+int avdb_cadd_update_write_host(const avdb_ctx* ctx, const uint8_t* text, size_t text_bytes, size_t n_lines,
+                                size_t n_rows, const avdb_cadd_table* snv, const avdb_cadd_table* indel,
+                                const char* chrom, size_t chrom_len, const uint64_t* row_start, const uint32_t* pk_len,
+                                const uint8_t* kind, const int32_t* match, const uint32_t* out_len,
+                                const uint8_t* row_flags, uint8_t* out, size_t out_cap, uint64_t* row_off,
+                                uint64_t* totals);
+int avdb_cadd_score_text_host(const uint8_t* text, size_t n, uint8_t* out, size_t cap, size_t* len);
+
 /* ---- K9: genome-piece sharding of VCF text --------------------------------
  * The reference runs one process per chromosome file (Load/bin/load_vcf_file.py:
  * 307-313).  One file is split over the ranks of a node by a piece plan
