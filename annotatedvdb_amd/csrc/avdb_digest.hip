@@ -617,9 +617,12 @@ constexpr int kSufTab = 72;  // windows at offsets -8 .. 63 from the suffix star
 // ALT word j of a block: 8 heap bytes from `at`.  CLAMP (a block reaching past
 // the heap end): the load starts at most at the last 8 heap bytes and is shifted
 // down (bytes past the heap end lie past the ALT and are masked off anyway).
-template <bool CLAMP>
+// TINY (a heap of fewer than 8 bytes, which holds no such load): bytewise.
+template <bool CLAMP, bool TINY>
 __device__ __forceinline__ uint64_t alt_word(const Heap& hp, uint64_t at) {
-  if constexpr (!CLAMP) {
+  if constexpr (TINY) {
+    return heap_u64(hp, at);
+  } else if constexpr (!CLAMP) {
     return reinterpret_cast<g_u64u>(hp.lo + at)->v;
   } else {
     const uint64_t lim = (hp.hi - hp.lo) - 8;
@@ -629,7 +632,7 @@ __device__ __forceinline__ uint64_t alt_word(const Heap& hp, uint64_t at) {
   }
 }
 
-template <bool CLAMP>
+template <bool CLAMP, bool TINY>
 __device__ __forceinline__ void allele_words(uint64_t* w, uint32_t ab, const uint64_t* locw, const Heap& hp,
                                              uint64_t altoff, int64_t Q, const uint64_t* s_suf) {
   const bool FIRST = ab == 0;  // uniform across the wave
@@ -656,7 +659,8 @@ __device__ __forceinline__ void allele_words(uint64_t* w, uint32_t ab, const uin
     }
     if (!FIRST || j >= 8) {
       // block 0 word 8: prefix bytes 64..67, then ALT bytes 0..3
-      const uint64_t x = (FIRST && j == 8) ? alt_word<CLAMP>(hp, altoff) << 32 : alt_word<CLAMP>(hp, b0 + 8 * j);
+      const uint64_t x =
+          (FIRST && j == 8) ? alt_word<CLAMP, TINY>(hp, altoff) << 32 : alt_word<CLAMP, TINY>(hp, b0 + 8 * j);
       const int64_t nbytes = Q - p;  // ALT bytes from the word start (<= 0: none)
       le |= nbytes >= 8 ? x : (nbytes > 0 ? x & low_bytes_mask(uint32_t(nbytes)) : 0ull);
     }
@@ -667,6 +671,7 @@ __device__ __forceinline__ void allele_words(uint64_t* w, uint32_t ab, const uin
   }
 }
 
+template <bool TINY>
 __device__ __forceinline__ void allele_block(uint64_t* w, uint32_t ab, const uint64_t* locw, const Heap& hp,
                                              uint64_t altoff, uint32_t a, uint64_t TA, uint32_t nb,
                                              const uint64_t* s_suf) {
@@ -679,17 +684,17 @@ __device__ __forceinline__ void allele_block(uint64_t* w, uint32_t ab, const uin
     const uint64_t b0 = altoff + 128 * uint64_t(ab) - kAlPrefix;
     if (hp.lo + b0 + 128 <= hp.hi) {
 #pragma unroll
-      for (int j = 0; j < 16; ++j) w[j] = __builtin_bswap64(alt_word<false>(hp, b0 + 8 * j));
+      for (int j = 0; j < 16; ++j) w[j] = __builtin_bswap64(alt_word<false, TINY>(hp, b0 + 8 * j));
     } else {
 #pragma unroll
-      for (int j = 0; j < 16; ++j) w[j] = __builtin_bswap64(alt_word<true>(hp, b0 + 8 * j));
+      for (int j = 0; j < 16; ++j) w[j] = __builtin_bswap64(alt_word<true, TINY>(hp, b0 + 8 * j));
     }
     return;
   }
   if (hp.lo + altoff + 128 * uint64_t(ab) + 128 <= hp.hi)
-    allele_words<false>(w, ab, locw, hp, altoff, Q, s_suf);
+    allele_words<false, TINY>(w, ab, locw, hp, altoff, Q, s_suf);
   else
-    allele_words<true>(w, ab, locw, hp, altoff, Q, s_suf);
+    allele_words<true, TINY>(w, ab, locw, hp, altoff, Q, s_suf);
   if (ab + 1 == nb) w[15] = TA * 8;  // (w[14], the high length word, is 0 from the table)
 }
 
@@ -741,6 +746,7 @@ struct KeyFill {
   uint8_t* key_out;
   uint8_t* state;
 };
+template <bool TINY>  // heap_bytes < 8 (alt_word)
 __global__ __launch_bounds__(kBlock, kDigestWavesPerSimd) void k_vrs_digest(
     const uint8_t* __restrict__ chrom, const uint32_t* __restrict__ pos,
     const uint64_t* __restrict__ off, const uint32_t* __restrict__ rl,
@@ -804,7 +810,7 @@ __global__ __launch_bounds__(kBlock, kDigestWavesPerSimd) void k_vrs_digest(
           w[2 * j + 1] = uint64_t(v.z) | (uint64_t(v.w) << 32);
         }
       } else {
-        allele_block(w, b - nbL, locw, hp, altoff, a, TA, nbA, s_suf);
+        allele_block<TINY>(w, b - nbL, locw, hp, altoff, a, TA, nbA, s_suf);
       }
       sha512_block(H, w);
       if (b + 1 == nbL) {  // location digest done: its chars feed the Allele blob
@@ -932,10 +938,10 @@ static int vrs_digest_impl(avdb_ctx* ctx, const uint8_t* chrom, const uint32_t* 
   // (a smaller grid leaves CUs to K7 running beside it: avdb_ctx_set_option)
   const int per_cu = ctx->k4_blocks_per_cu < kDigestWavesPerSimd ? ctx->k4_blocks_per_cu : kDigestWavesPerSimd;
   const unsigned grid = ctx->k4_grid > 0 ? unsigned(ctx->k4_grid) : unsigned(ctx->n_cu * per_cu);
-  hipLaunchKernelGGL(k_vrs_digest, dim3(grid), dim3(kBlock), 0, s, chrom, pos,
-                     allele_off,
-                     ref_len, alt_len, heap, heap_bytes, list, total, ctx->d_seq_digest, ctx->d_loc_tail,
-                     ctx->tab.n, digest_out, fill);
+  // (a heap of fewer than 8 bytes holds no 8-byte load: its kernel reads the ALT bytewise, alt_word)
+  hipLaunchKernelGGL(heap_bytes < 8 ? k_vrs_digest<true> : k_vrs_digest<false>, dim3(grid), dim3(kBlock), 0, s,
+                     chrom, pos, allele_off, ref_len, alt_len, heap, heap_bytes, list, total, ctx->d_seq_digest,
+                     ctx->d_loc_tail, ctx->tab.n, digest_out, fill);
   AVDB_LAUNCH_CHECK("k_vrs_digest");
   return AVDB_OK;
 }
