@@ -75,6 +75,11 @@ CADDUPD_CHROM_MAX, CADDUPD_SCORE_MAX = 64, 24
 CADDUPD_COUNTS = ("rows", "skipped_lines", "skipped", "snv", "indel", "not_matched", "host_rows", "bad", "lone_cr",
                   "out_bytes")  # AVDB_CADDUPD_COUNT_*, by slot
 CADDUPD_N_COUNTS = len(CADDUPD_COUNTS)
+EXPVCF_ROW_HOST, EXPVCF_BAD, EXPVCF_DROPPED = 1, 2, 4  # AVDB_EXPVCF_* row flags
+EXPVCF_STREAM_VCF, EXPVCF_STREAM_INVALID = 0, 1
+EXPVCF_COUNTS = ("valid", "invalid", "skipped_lines", "filtered", "bad", "lone_cr", "vcf_bytes",
+                 "invalid_bytes")  # AVDB_EXPVCF_COUNT_*, by slot
+EXPVCF_N_COUNTS = len(EXPVCF_COUNTS)
 MAX_ALG_ID = 64
 BGZF_STATUS = ("OK", "bad header", "input overrun", "bad block type", "bad stored length", "bad code lengths",
                "bad symbol", "distance before block start", "output longer than ISIZE", "output shorter than ISIZE",
@@ -151,6 +156,8 @@ EXPORTED_SYMBOLS = [
     "avdb_existing_size_host", "avdb_existing_write_host",
     "avdb_cadd_update_workspace_size", "avdb_cadd_update_size", "avdb_cadd_update_write",
     "avdb_cadd_update_size_host", "avdb_cadd_update_write_host", "avdb_cadd_score_text_host",
+    "avdb_export_vcf_workspace_size", "avdb_export_vcf_size", "avdb_export_vcf_write",
+    "avdb_export_vcf_size_host", "avdb_export_vcf_write_host",
 ]
 
 
@@ -294,6 +301,11 @@ def _sig(lib):
     f.avdb_cadd_update_write_host.argtypes = [P, P, SZ, SZ, SZ, T, T, ctypes.c_char_p, SZ, P, P, P, P, P, P, P, SZ, P, P]
     f.avdb_cadd_update_write.argtypes = f.avdb_cadd_update_write_host.argtypes + [P, SZ, P]
     f.avdb_cadd_score_text_host.argtypes = [P, SZ, P, SZ, ctypes.POINTER(SZ)]
+    f.avdb_export_vcf_workspace_size.argtypes = [SZ, SZ, ctypes.POINTER(SZ)]
+    f.avdb_export_vcf_size_host.argtypes = [P, P, SZ, SZ, U32] + [P] * 10
+    f.avdb_export_vcf_size.argtypes = f.avdb_export_vcf_size_host.argtypes + [P, SZ, P]
+    f.avdb_export_vcf_write_host.argtypes = [P, P, SZ, SZ, U32, SZ, P, P, P, P, P, P, SZ, P, P]
+    f.avdb_export_vcf_write.argtypes = f.avdb_export_vcf_write_host.argtypes + [P, SZ, P]
     for name in EXPORTED_SYMBOLS:
         if name not in ("avdb_last_error",):
             getattr(f, name).restype = I32

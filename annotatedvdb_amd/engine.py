@@ -132,6 +132,54 @@ class CaddUpdateRows:
     counts: Dict[str, int]
 
 
+VCF_EXPORT_HEADER = b"#CHRM\tPOS\tID\tREF\tALT\tQUAL\tFILTER\tINFO\n"  # (sic) export_variant2vcf.py:26
+
+_FILE_SALT = -7046029254386353131  # 0x9E3779B97F4A7C15 as int64: folds a row's file number into its key hash (K14)
+
+
+@dataclass
+class ExportVcf:
+    """What K14 makes of an export of ``AnnotatedVDB.Variant`` (:meth:`Engine.export_vcf`):
+    ``vcf_text`` holds the rows of all ``n_files`` VCF files back to back, without their
+    header lines (valid row ``v`` at ``vcf_row_off[v] .. vcf_row_off[v + 1]``; a row whose
+    key repeats an earlier one of its file has no bytes), ``invalid_text`` the rows of the
+    invalid file (``pk<TAB>alg<LF>``) with ``invalid_row_off``, ``flags`` the valid rows'
+    ``N.EXPVCF_*`` flags, ``counts`` the pass's counts by name (``N.EXPVCF_COUNTS``, and
+    ``dropped``: the rows a repeated key removed)."""
+    vcf_text: torch.Tensor
+    vcf_row_off: torch.Tensor
+    invalid_text: torch.Tensor
+    invalid_row_off: torch.Tensor
+    flags: torch.Tensor
+    counts: Dict[str, int]
+    n_files: int
+    variants_per_file: int
+    file_start: List[int]  # n_files + 1 offsets into vcf_text
+
+    def file_span(self, k: int) -> Tuple[int, int]:
+        """``(begin, end)`` of file ``k`` (1 .. ``n_files``) in ``vcf_text``."""
+        if not 1 <= k <= self.n_files:
+            raise IndexError(f"file {k} of {self.n_files}")
+        return self.file_start[k - 1], self.file_start[k]
+
+    def files(self, directory: str, chromosome: str) -> List[str]:
+        """Writes ``<chromosome>_<k>.vcf`` (the header line, then the file's rows) for
+        every file and ``<chromosome>_invalid.txt``, named as ``export_variant2vcf.py``
+        names them (``:30,40``); returns the paths."""
+        vcf = self.vcf_text.cpu().numpy()
+        paths = []
+        for k in range(1, self.n_files + 1):
+            b, e = self.file_span(k)
+            paths.append(os.path.join(directory, "%s_%d.vcf" % (chromosome, k)))
+            with open(paths[-1], "wb") as fh:
+                fh.write(VCF_EXPORT_HEADER)
+                fh.write(vcf[b:e].tobytes())
+        paths.append(os.path.join(directory, chromosome + "_invalid.txt"))
+        with open(paths[-1], "wb") as fh:
+            fh.write(self.invalid_text.cpu().numpy().tobytes())
+        return paths
+
+
 def existing_contig_mask(contigs) -> int:
     """K12's contig mask: ``None`` keeps every row; otherwise one bit per label of
     ``contigs`` (``CHROM_NAMES`` index; bit 31 for any other label)."""
@@ -1516,6 +1564,123 @@ class Engine:
             raise N.NativeError("avdb_cadd_update_write" + suffix, N.AVDB_ERANGE,
                                 f"rows of {tot[0]} bytes do not fit the {out_bytes} the size pass gave")
         return CaddUpdateRows(n, out_text[:out_bytes], row_off, kind[:n], flags[:n], cnt)
+
+    # -- K14: the VCF files of an export ------------------------------------------
+    def export_vcf(self, text, contigs=None, variants_per_file: int = 10_000_000) -> "ExportVcf":
+        """K14: a slab of an export in the column order of ``export_variant2vcf.py``'s
+        ``SELECT_SQL`` (``record_primary_key<TAB>metaseq_id<TAB>row_algorithm_id[<TAB>...]``
+        lines; bytes, numpy ``uint8`` or a ``uint8`` tensor) -> :class:`ExportVcf` on this
+        engine's device: the rows of the VCF files the reference's ``run`` writes for the
+        same records, ``variants_per_file`` valid records to a file, and the rows of its
+        invalid file.  ``contigs``: labels of the metaseq ids whose rows to keep
+        (``None``: all), as for :meth:`existing_table_build`.  Three syncs: the line
+        count, the size pass's counts (the outputs are allocated from them), the end.
+        The reference keeps a file's rows in a dict keyed by primary key: rows of one
+        file whose keys hash alike (found by sorting ``(file, pk_hash)``) have their key
+        bytes fetched and compared here, and of true repeats the first is rendered here
+        with the last one's metaseq id and the others are dropped; the VCF write pass
+        then runs again.  Without such rows no row text comes to the host.  On a
+        host-only engine the library's host entries run the same per-line code."""
+        vpf = int(variants_per_file)
+        if vpf < 1:
+            raise ValueError("variants_per_file must be at least 1")
+        text = self._as_text(text)
+        nb = text.numel()
+        n_lines = self._count_lines(text)
+        m = max(1, n_lines)
+        row_start, pk_hash, inv_start = (self.empty(m, torch.int64) for _ in range(3))
+        pk_len, ms_len, out_len, inv_pk_len, inv_out_len = (self.empty(m, torch.int32) for _ in range(5))
+        flags = self.empty(m, torch.uint8)
+        counts = self.empty(N.EXPVCF_N_COUNTS, torch.int64)
+        tp = text if nb else None
+        if self.host_only:
+            run, suffix, tail = self._call, "_host", ()
+        else:
+            ws = self.scratch("export_vcf", N.size("avdb_export_vcf_workspace_size", nb, n_lines))
+            run, suffix, tail = self._launch, "", (ws, ws.numel())
+        run("avdb_export_vcf_size" + suffix, tp, nb, n_lines, existing_contig_mask(contigs), row_start, pk_len, ms_len,
+            out_len, flags, pk_hash, inv_start, inv_pk_len, inv_out_len, counts, *tail)
+        cnt = dict(zip(N.EXPVCF_COUNTS, (int(x) for x in counts.cpu().numpy().astype(np.uint64))))
+        if cnt["lone_cr"]:
+            raise ValueError(f"{cnt['lone_cr']} carriage return(s) in the export that no newline follows: Python's "
+                             "text mode ends a line there and the device pass does not")
+        nv, ni = cnt["valid"], cnt["invalid"]
+        if cnt["bad"]:
+            first = int(row_start[:nv][(flags[:nv] & N.EXPVCF_BAD) != 0][0])
+            line = int((text[:first] == 10).sum()) + 1
+            raise ValueError(f"line {line} of the export: the metaseq id does not have the four parts "
+                             f"chrom:pos:ref:alt ({cnt['bad']} such line(s))")
+        n_files = nv // vpf + 1
+        # rows of one file whose keys hash alike: neighbours after one sort of the hash with the file folded in
+        # (equal (file, hash) pairs give equal sort keys; the host compare below sorts out any other)
+        order = same = None
+        n_cand = torch.zeros(1, dtype=torch.int64, device=self.device)
+        if nv > 1:
+            key = pk_hash[:nv]
+            if n_files > 1:
+                key = key + torch.div(torch.arange(nv, device=self.device), vpf, rounding_mode="floor") * _FILE_SALT
+            skey, order = torch.sort(key)
+            same = skey[1:] == skey[:-1]
+            n_cand = same.sum().view(1)
+        cnt["dropped"] = 0
+        file_rows = torch.arange(n_files, device=self.device) * vpf
+
+        def write(which, n, cols, nbytes):
+            out = self.empty(max(1, nbytes), torch.uint8)
+            row_off = self.empty(n + 1, torch.int64)
+            totals = self.empty(2, torch.int64)
+            run("avdb_export_vcf_write" + suffix, tp, nb, n_lines, which, n, *cols, out, nbytes, row_off, totals, *tail)
+            return out, row_off, totals
+
+        def check(name, tot, want):
+            if tot[1] or tot[0] != want:
+                raise N.NativeError("avdb_export_vcf_write" + suffix, N.AVDB_ERANGE,
+                                    f"{name} rows of {tot[0]} bytes do not fit the {want} the size pass gave")
+
+        vcf_cols = (row_start, pk_len, ms_len, out_len, flags)
+        vcf, vcf_off, vcf_tot = write(N.EXPVCF_STREAM_VCF, nv, vcf_cols, cnt["vcf_bytes"])
+        inv, inv_off, inv_tot = write(N.EXPVCF_STREAM_INVALID, ni, (inv_start, inv_pk_len, None, inv_out_len, None),
+                                      cnt["invalid_bytes"])
+        end = torch.cat([vcf_tot, inv_tot, n_cand, vcf_off[file_rows]]).cpu().tolist()
+        check("VCF", end[0:2], cnt["vcf_bytes"])
+        check("invalid", end[2:4], cnt["invalid_bytes"])
+        file_start = end[5:]
+        if end[4]:
+            member = torch.zeros(nv, dtype=torch.bool, device=self.device)
+            member[order[1:][same]] = True
+            member[order[:-1][same]] = True
+            rows = torch.nonzero(member).flatten()  # in file order
+            pl, ml = pk_len[rows].long(), ms_len[rows].long()
+            raw = text[self._spans(row_start[rows], pl + 1 + ml)].cpu().numpy().tobytes()
+            groups, at = {}, 0  # (file, key bytes) -> [(row, metaseq id)]
+            for r, p, q in zip(rows.tolist(), pl.tolist(), ml.tolist()):
+                groups.setdefault((r // vpf, raw[at:at + p]), []).append((r, raw[at + p + 1:at + p + 1 + q]))
+                at += p + 1 + q
+            first, rendered, dropped = [], [], []
+            for (_, pk), g in groups.items():
+                if len(g) > 1:  # variants[primaryKey] = metaseqId: the first one's place, the last one's id
+                    c, p, r, a = g[-1][1].split(b":")
+                    first.append(g[0][0])
+                    rendered.append(b"\t".join((c, p, pk, r, a, b".", b".", b".")) + b"\n")
+                    dropped += [x[0] for x in g[1:]]
+            if first:
+                first_t, dropped_t = (torch.tensor(x, dtype=torch.int64, device=self.device) for x in (first, dropped))
+                new_len = torch.tensor([len(x) for x in rendered], dtype=torch.int64)
+                cnt["vcf_bytes"] += int(new_len.sum()) - int(out_len[first_t].sum()) - int(out_len[dropped_t].sum())
+                cnt["dropped"] = len(dropped)
+                flags[first_t] |= N.EXPVCF_ROW_HOST
+                flags[dropped_t] |= N.EXPVCF_DROPPED
+                out_len[first_t] = new_len.to(torch.int32).to(self.device)
+                out_len[dropped_t] = 0
+                vcf, vcf_off, vcf_tot = write(N.EXPVCF_STREAM_VCF, nv, vcf_cols, cnt["vcf_bytes"])
+                blob = torch.from_numpy(np.frombuffer(b"".join(rendered), dtype=np.uint8).copy()).to(self.device)
+                vcf[self._spans(vcf_off[first_t], new_len.to(self.device))] = blob
+                end = torch.cat([vcf_tot, vcf_off[file_rows]]).cpu().tolist()
+                check("VCF", end[0:2], cnt["vcf_bytes"])
+                file_start = end[2:]
+        file_start = [int(x) for x in file_start] + [cnt["vcf_bytes"]]
+        return ExportVcf(vcf[:cnt["vcf_bytes"]], vcf_off, inv[:cnt["invalid_bytes"]], inv_off, flags[:nv], cnt, n_files,
+                         vpf, file_start)
 
     # -- K10: CADD table and allele join ---------------------------------------
     def new_cadd_counters(self) -> torch.Tensor:

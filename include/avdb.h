@@ -1009,6 +1009,90 @@ int avdb_cadd_update_write_host(const avdb_ctx* ctx, const uint8_t* text, size_t
                                 uint64_t* totals);
 int avdb_cadd_score_text_host(const uint8_t* text, size_t n, uint8_t* out, size_t cap, size_t* len);
 
+/* ---- K14: the per-chromosome VCF files of a variant export ----------------------
+ * Replaces the per-record host code of Util/bin/export_variant2vcf.py (run, :63-97, and
+ * print_file, :29-35): `text` is a slab of an export in the column order of the
+ * reference's SELECT_SQL (:23),
+ * `record_primary_key<TAB>metaseq_id<TAB>row_algorithm_id[<TAB>...]` lines separated by
+ * '\n' (n_lines as for K0, K10a, K12 and K13), and the output is two texts: the rows of
+ * the chrN_<k>.vcf files, in file order and without their header lines, and the rows of
+ * chrN_invalid.txt.
+ * Row rule (K13's): one trailing '\r' before the '\n' is stripped; an empty line, a line
+ * with fewer than two fields and a line whose first field is exactly
+ * `record_primary_key` are no row (counts[AVDB_EXPVCF_COUNT_SKIPPED_LINES]); fields after
+ * the third are ignored.  A '\r' no '\n' follows is counted (AVDB_EXPVCF_COUNT_LONE_CR)
+ * and the caller decides.  contig_mask: as for K12 and K13, over the label of the metaseq
+ * id (the text before its first ':'); a line whose bit is clear is skipped as if it were
+ * absent (AVDB_EXPVCF_COUNT_FILTERED).  Every other line is a row of one of two lists,
+ * each in file order:
+ *   - invalid: the metaseq id holds one of the bytes I, R, D, N anywhere (the
+ *     reference's matches('I|R|D|N', metaseqId), taken as re.search; tested before
+ *     anything else of the id).  Its text is `pk<TAB>alg<LF>`; alg is the third field
+ *     verbatim, or `None` (how Python prints NULL) when that field is absent, empty or
+ *     `\N`.  The reference reads a cursor, not text: that these three spell NULL is this
+ *     project's choice, the one K13 makes for cadd_scores.
+ *   - valid: every other row.  Its text is
+ *     `label<TAB>pos<TAB>pk<TAB>ref<TAB>alt<TAB>.<TAB>.<TAB>.<LF>`, len(metaseq_id) +
+ *     len(pk) + 8 bytes; the key and the four parts of the id are copied verbatim
+ *     (backslashes too).  A valid row whose id does not have exactly three ':' is
+ *     flagged AVDB_EXPVCF_BAD (no output; the reference's four-way unpack raises there).
+ *     pk_hash: K6's 64-bit string hash of the key bytes, for the caller's search for
+ *     repeated keys (the reference keeps a file's rows in a dict keyed by primary key).
+ * Valid row v (BAD rows counted) belongs to file v / variants_per_file + 1, so the VCF
+ * text of file k starts at row_off[(k - 1) * variants_per_file]; the split and the header
+ * lines are the caller's.
+ *   1. avdb_export_vcf_size: per valid row (n_lines entries allocated, rows written)
+ *      row_start (u64: the offset of the row's line in the slab), pk_len, ms_len,
+ *      out_len, row_flags, pk_hash; per invalid row inv_start, inv_pk_len, inv_out_len;
+ *      counts (AVDB_EXPVCF_N_COUNTS x u64, set by the call).
+ *   2. avdb_export_vcf_write, once per stream (`which`: AVDB_EXPVCF_STREAM_VCF with the
+ *      valid rows' arrays, AVDB_EXPVCF_STREAM_INVALID with the invalid rows' and ms_len =
+ *      row_flags = NULL; the same text): scans out_len into row_off (n_rows + 1 entries)
+ *      and writes the rows to out (8-byte aligned, out_cap bytes).  Before it the caller
+ *      may flag a valid row AVDB_EXPVCF_ROW_HOST and store the row's length in out_len
+ *      (the row's span is filled with spaces, for the caller to overwrite after the
+ *      pass), or AVDB_EXPVCF_DROPPED and store 0 (nothing is written for the row).
+ *      totals (2 x u64): the bytes of all rows, and 1 when they exceed out_cap.  Nothing
+ *      outside [0, total) is written, and nothing at all when out_cap is too small: the
+ *      host entry returns AVDB_ERANGE then; the device entry, which does not wait for its
+ *      own scan, returns AVDB_OK and leaves totals[1] != 0 for the caller to read after
+ *      the stream.
+ * Workspace: avdb_export_vcf_workspace_size bytes, 256-byte aligned; the device entries
+ * allocate nothing per call.  The _host entries run the same per-line code on host
+ * pointers, on an avdb_ctx_create(-1, ...) context. */
+#define AVDB_EXPVCF_ROW_HOST 0x01u
+#define AVDB_EXPVCF_BAD 0x02u
+#define AVDB_EXPVCF_DROPPED 0x04u
+#define AVDB_EXPVCF_STREAM_VCF 0u
+#define AVDB_EXPVCF_STREAM_INVALID 1u
+#define AVDB_EXPVCF_COUNT_VALID 0          /* BAD rows included */
+#define AVDB_EXPVCF_COUNT_INVALID 1
+#define AVDB_EXPVCF_COUNT_SKIPPED_LINES 2  /* lines that are no row and not filtered */
+#define AVDB_EXPVCF_COUNT_FILTERED 3       /* lines of contigs outside contig_mask */
+#define AVDB_EXPVCF_COUNT_BAD 4
+#define AVDB_EXPVCF_COUNT_LONE_CR 5
+#define AVDB_EXPVCF_COUNT_VCF_BYTES 6
+#define AVDB_EXPVCF_COUNT_INVALID_BYTES 7
+#define AVDB_EXPVCF_N_COUNTS 8
+int avdb_export_vcf_workspace_size(size_t text_bytes, size_t n_lines, size_t* bytes);
+int avdb_export_vcf_size(avdb_ctx* ctx, const uint8_t* text, size_t text_bytes, size_t n_lines, uint32_t contig_mask,
+                         uint64_t* row_start, uint32_t* pk_len, uint32_t* ms_len, uint32_t* out_len,
+                         uint8_t* row_flags, uint64_t* pk_hash, uint64_t* inv_start, uint32_t* inv_pk_len,
+                         uint32_t* inv_out_len, uint64_t* counts, void* workspace, size_t workspace_bytes,
+                         void* stream);
+int avdb_export_vcf_write(avdb_ctx* ctx, const uint8_t* text, size_t text_bytes, size_t n_lines, uint32_t which,
+                          size_t n_rows, const uint64_t* row_start, const uint32_t* pk_len, const uint32_t* ms_len,
+                          const uint32_t* out_len, const uint8_t* row_flags, uint8_t* out, size_t out_cap,
+                          uint64_t* row_off, uint64_t* totals, void* workspace, size_t workspace_bytes, void* stream);
+int avdb_export_vcf_size_host(const avdb_ctx* ctx, const uint8_t* text, size_t text_bytes, size_t n_lines,
+                              uint32_t contig_mask, uint64_t* row_start, uint32_t* pk_len, uint32_t* ms_len,
+                              uint32_t* out_len, uint8_t* row_flags, uint64_t* pk_hash, uint64_t* inv_start,
+                              uint32_t* inv_pk_len, uint32_t* inv_out_len, uint64_t* counts);
+int avdb_export_vcf_write_host(const avdb_ctx* ctx, const uint8_t* text, size_t text_bytes, size_t n_lines,
+                               uint32_t which, size_t n_rows, const uint64_t* row_start, const uint32_t* pk_len,
+                               const uint32_t* ms_len, const uint32_t* out_len, const uint8_t* row_flags, uint8_t* out,
+                               size_t out_cap, uint64_t* row_off, uint64_t* totals);
+
 /* ---- K9: genome-piece sharding of VCF text --------------------------------
  * The reference runs one process per chromosome file (Load/bin/load_vcf_file.py:
  * 307-313).  One file is split over the ranks of a node by a piece plan
