@@ -80,6 +80,11 @@ EXPVCF_STREAM_VCF, EXPVCF_STREAM_INVALID = 0, 1
 EXPVCF_COUNTS = ("valid", "invalid", "skipped_lines", "filtered", "bad", "lone_cr", "vcf_bytes",
                  "invalid_bytes")  # AVDB_EXPVCF_COUNT_*, by slot
 EXPVCF_N_COUNTS = len(EXPVCF_COUNTS)
+SPLIT_N_STREAMS, SPLIT_OTHER, SPLIT_NONE = 26, 25, 0xFF  # AVDB_SPLIT_*
+SPLIT_LINE_HOST = 0x80000000  # bit 31 of a line's out_len
+SPLIT_COUNT_LINES, SPLIT_COUNT_BYTES, SPLIT_COUNT_COMMENTS, SPLIT_COUNT_HOST_LINES, SPLIT_COUNT_FIRST_OTHER = \
+    0, 26, 52, 53, 54
+SPLIT_N_COUNTS = 55
 MAX_ALG_ID = 64
 BGZF_STATUS = ("OK", "bad header", "input overrun", "bad block type", "bad stored length", "bad code lengths",
                "bad symbol", "distance before block start", "output longer than ISIZE", "output shorter than ISIZE",
@@ -158,6 +163,8 @@ EXPORTED_SYMBOLS = [
     "avdb_cadd_update_size_host", "avdb_cadd_update_write_host", "avdb_cadd_score_text_host",
     "avdb_export_vcf_workspace_size", "avdb_export_vcf_size", "avdb_export_vcf_write",
     "avdb_export_vcf_size_host", "avdb_export_vcf_write_host",
+    "avdb_vcf_split_workspace_size", "avdb_vcf_split_size", "avdb_vcf_split_write",
+    "avdb_vcf_split_size_host", "avdb_vcf_split_write_host",
 ]
 
 
@@ -306,6 +313,11 @@ def _sig(lib):
     f.avdb_export_vcf_size.argtypes = f.avdb_export_vcf_size_host.argtypes + [P, SZ, P]
     f.avdb_export_vcf_write_host.argtypes = [P, P, SZ, SZ, U32, SZ, P, P, P, P, P, P, SZ, P, P]
     f.avdb_export_vcf_write.argtypes = f.avdb_export_vcf_write_host.argtypes + [P, SZ, P]
+    f.avdb_vcf_split_workspace_size.argtypes = [SZ, SZ, ctypes.POINTER(SZ)]
+    f.avdb_vcf_split_size_host.argtypes = [P, P, SZ, SZ, P, P, P, P, P]
+    f.avdb_vcf_split_size.argtypes = f.avdb_vcf_split_size_host.argtypes + [P, SZ, P]
+    f.avdb_vcf_split_write_host.argtypes = [P, P, SZ, SZ, P, P, P, P, SZ, P, P, P]
+    f.avdb_vcf_split_write.argtypes = f.avdb_vcf_split_write_host.argtypes + [P, SZ, P]
     for name in EXPORTED_SYMBOLS:
         if name not in ("avdb_last_error",):
             getattr(f, name).restype = I32

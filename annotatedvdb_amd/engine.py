@@ -180,6 +180,47 @@ class ExportVcf:
         return paths
 
 
+VCF_SPLIT_HEADER = b"#CHROM\tPOS\tID\tREF\tALT\tQUAL\tFILTER\tINFO\n"  # split_vcf_by_chr.py:17
+
+
+@dataclass
+class SplitVcf:
+    """What K15 makes of a slab of a whole-genome VCF (:meth:`Engine.split_vcf`): ``text``
+    holds 26 streams back to back, the data lines of ``chr1.vcf`` ... ``chrM.vcf``
+    (``CHROM_NAMES`` order) and, as stream 25, the lines no file takes (``unknown="keep"``
+    only); stream ``c`` is ``text[stream_off[c]:stream_off[c + 1]]``.  ``counts``: ``lines``
+    and ``bytes`` (26 each), ``comments``, ``host_lines`` (the lines whose stripped end the
+    host decided); ``first_other``: the index of the first line of stream 25, or ``None``."""
+    text: torch.Tensor
+    stream_off: List[int]  # 27 offsets into text
+    counts: Dict[str, object]
+    first_other: Optional[int]
+
+    def stream(self, c: int) -> torch.Tensor:
+        """Stream ``c`` (0 .. 25) as a slice of ``text``."""
+        if not 0 <= c < N.SPLIT_N_STREAMS:
+            raise IndexError(f"stream {c} of {N.SPLIT_N_STREAMS}")
+        return self.text[self.stream_off[c]:self.stream_off[c + 1]]
+
+    @property
+    def other_text(self) -> torch.Tensor:
+        return self.stream(N.SPLIT_OTHER)
+
+    def append_files(self, directory: str, first: bool) -> List[str]:
+        """Appends every stream 0..24 to ``chr<label>.vcf`` in ``directory``; with ``first``
+        the files are created and begin with the header line, as ``create_fh_dict``
+        (split_vcf_by_chr.py:14-22) writes it.  Returns the 25 paths."""
+        host = self.text[:self.stream_off[N.SPLIT_OTHER]].cpu().numpy()
+        paths = []
+        for c, label in enumerate(CHROM_NAMES[:N.SPLIT_OTHER]):
+            paths.append(os.path.join(directory, "chr%s.vcf" % label))
+            with open(paths[-1], "wb" if first else "ab") as fh:
+                if first:
+                    fh.write(VCF_SPLIT_HEADER)
+                fh.write(host[self.stream_off[c]:self.stream_off[c + 1]].tobytes())
+        return paths
+
+
 def existing_contig_mask(contigs) -> int:
     """K12's contig mask: ``None`` keeps every row; otherwise one bit per label of
     ``contigs`` (``CHROM_NAMES`` index; bit 31 for any other label)."""
@@ -638,6 +679,29 @@ class ChromMap:
             ok = c < len(names) and names[c] == chrom and isinstance(to_numeric(k), str)
             keys.append(kb)
             codes.append(c if ok else 0xFF)
+        self._create(keys, codes)
+
+    @classmethod
+    def for_split(cls, engine: "Engine", mapping: Dict) -> "ChromMap":
+        """The map by the rule of ``split_vcf_by_chr.py:44-50`` (K15): the code of a
+        source id is the index of ``mapping[id]`` among the 25 file labels when it is
+        exactly one of them, else 0xFF (no file: the reference's ``KeyError``).  No
+        'MT' -> 'M' step and no numeric coercion of the key: the script looks the text
+        of the first field up as it is."""
+        from .chromosomes import CHROM_NAMES as names
+        self = cls.__new__(cls)
+        self.eng, self.mapping = engine, mapping
+        keys, codes = [], []
+        for k, v in mapping.items():
+            if not isinstance(k, str):
+                continue
+            keys.append(k.encode("utf-8"))
+            codes.append(names.index(v) if isinstance(v, str) and v in names else 0xFF)
+        self._create(keys, codes)
+        return self
+
+    def _create(self, keys, codes):
+        engine = self.eng
         off = np.zeros(len(keys) + 1, dtype=np.uint64)
         if keys:
             off[1:] = np.cumsum([len(k) for k in keys])
@@ -1681,6 +1745,127 @@ class Engine:
         file_start = [int(x) for x in file_start] + [cnt["vcf_bytes"]]
         return ExportVcf(vcf[:cnt["vcf_bytes"]], vcf_off, inv[:cnt["invalid_bytes"]], inv_off, flags[:nv], cnt, n_files,
                          vpf, file_start)
+
+    # -- K15: a whole-genome VCF split by chromosome ------------------------------
+    def split_chrom_map(self, mapping: Dict) -> "ChromMap":
+        """A ChromosomeMap's dict as the library map of K15's rule (:meth:`ChromMap.for_split`),
+        cached per dict."""
+        cache = self.__dict__.setdefault("_split_maps", {})
+        cm = cache.get(id(mapping))
+        if cm is None or cm.mapping is not mapping:
+            cm = cache[id(mapping)] = ChromMap.for_split(self, mapping)
+        return cm
+
+    def split_vcf(self, text, chrom_map=None, unknown: str = "raise") -> "SplitVcf":
+        """K15: a '\\n'-separated slab of a VCF (bytes, numpy ``uint8`` or a ``uint8``
+        tensor) -> :class:`SplitVcf` on this engine's device: the lines
+        ``split_vcf_by_chr.py``'s ``run`` prints to ``chr1.vcf`` ... ``chrM.vcf`` for the
+        same text, per file and in file order.  ``chrom_map``: a :class:`ChromMap` made by
+        :meth:`ChromMap.for_split` (or the ChromosomeMap's dict) when CHROM holds source
+        ids, ``None`` when it holds the labels.  A line no file takes raises the
+        reference's ``KeyError`` (``unknown="raise"``; the error's ``line`` is the line's
+        1-based number in the slab) or goes to stream 25 (``unknown="keep"``).  Three
+        syncs: the line count, the size pass's counts (the blob is allocated from them),
+        the end.  Lines whose stripped end Python may see differently (a last byte of
+        0x1C..0x1F or >= 0x80) are fetched and decided here by
+        ``line.decode("utf-8").rstrip()``, whose ``UnicodeDecodeError`` propagates when no
+        unplaced line comes before it; invalid UTF-8 elsewhere in a line is copied
+        verbatim.  On a host-only engine the library's host entries run the same
+        per-line code."""
+        if unknown not in ("raise", "keep"):
+            raise ValueError("unknown must be 'raise' or 'keep'")
+        if isinstance(chrom_map, dict):
+            chrom_map = self.split_chrom_map(chrom_map)
+        text = self._as_text(text)
+        nb = text.numel()
+        n_lines = self._count_lines(text)
+        m = max(1, n_lines)
+        code = self.empty(m, torch.uint8)
+        line_start = self.empty(m, torch.int64)
+        out_len = self.empty(m, torch.int32)
+        counts = self.empty(N.SPLIT_N_COUNTS, torch.int64)
+        tp = text if nb else None
+        handle = chrom_map.handle if chrom_map is not None else None
+        if self.host_only:
+            run, suffix, tail = self._call, "_host", ()
+        else:
+            ws = self.scratch("split_vcf", N.size("avdb_vcf_split_workspace_size", nb, n_lines))
+            run, suffix, tail = self._launch, "", (ws, ws.numel())
+        run("avdb_vcf_split_size" + suffix, tp, nb, n_lines, handle, code, line_start, out_len, counts, *tail)
+        cnt = [int(x) for x in counts.cpu().numpy().astype(np.uint64)]
+        n_of = cnt[N.SPLIT_COUNT_LINES:N.SPLIT_COUNT_LINES + N.SPLIT_N_STREAMS]
+        b_of = cnt[N.SPLIT_COUNT_BYTES:N.SPLIT_COUNT_BYTES + N.SPLIT_N_STREAMS]
+        comments, host_lines = cnt[N.SPLIT_COUNT_COMMENTS], cnt[N.SPLIT_COUNT_HOST_LINES]
+        first_other = cnt[N.SPLIT_COUNT_FIRST_OTHER] if n_of[N.SPLIT_OTHER] else None
+        mapping = chrom_map.mapping if chrom_map is not None else None
+
+        def stream_of_key(key: str) -> int:
+            label = key if mapping is None else mapping.get(key)
+            return CHROM_NAMES.index(label) if isinstance(label, str) and label in CHROM_NAMES else N.SPLIT_OTHER
+
+        decode_error = None  # (line, the UnicodeDecodeError) of the first line whose decode raises
+        if host_lines:
+            rows = torch.nonzero(out_len[:n_lines] < 0).flatten()  # bit 31: N.SPLIT_LINE_HOST
+            begin = line_start[rows]
+            end = torch.where(rows + 1 < n_lines, line_start[torch.clamp(rows + 1, max=n_lines - 1)],
+                              torch.full_like(begin, nb))
+            raw = text[self._spans(begin, end - begin)].cpu().numpy().tobytes()
+            old_code, old_len = code[rows].cpu().tolist(), (out_len[rows] & 0x7FFFFFFF).cpu().tolist()
+            new_code, new_len, at = [], [], 0
+            for i, (r, span) in enumerate(zip(rows.tolist(), (end - begin).tolist())):
+                line = raw[at:at + span]
+                at += span
+                try:
+                    line = line.decode("utf-8").rstrip()
+                except UnicodeDecodeError as e:
+                    if decode_error is None:
+                        decode_error = (r, e)
+                    new_code.append(old_code[i])
+                    new_len.append(old_len[i])
+                    continue
+                if line.startswith("#"):
+                    c, ln = N.SPLIT_NONE, 0
+                else:
+                    c, ln = stream_of_key(line.split("\t")[0]), len(line.encode("utf-8")) + 1
+                new_code.append(c)
+                new_len.append(ln)
+                if old_code[i] < N.SPLIT_N_STREAMS:
+                    n_of[old_code[i]] -= 1
+                    b_of[old_code[i]] -= old_len[i]
+                else:
+                    comments -= 1
+                if c < N.SPLIT_N_STREAMS:
+                    n_of[c] += 1
+                    b_of[c] += ln
+                else:
+                    comments += 1
+            code[rows] = torch.tensor(new_code, dtype=torch.uint8).to(self.device)
+            out_len[rows] = torch.tensor(new_len, dtype=torch.int32).to(self.device)
+            others = torch.nonzero(code[:n_lines] == N.SPLIT_OTHER).flatten()
+            first_other = int(others[0]) if others.numel() else None
+        if decode_error is not None and (unknown == "keep" or first_other is None or decode_error[0] < first_other):
+            raise decode_error[1]
+        if first_other is not None and unknown == "raise":
+            b = int(line_start[first_other])
+            line = text[b:b + int(out_len[first_other] & 0x7FFFFFFF) - 1].cpu().numpy().tobytes()
+            key = line.decode("utf-8", "replace").split("\t")[0]
+            err = KeyError(key if mapping is None or key not in mapping else mapping[key])
+            err.line = first_other + 1
+            if hasattr(err, "add_note"):
+                err.add_note(f"line {err.line} of the slab: no chr<label>.vcf takes it")
+            raise err
+        total = sum(b_of)
+        out = self.empty(max(1, total), torch.uint8)
+        stream_off = self.empty(N.SPLIT_N_STREAMS + 1, torch.int64)
+        totals = self.empty(2, torch.int64)
+        run("avdb_vcf_split_write" + suffix, tp, nb, n_lines, code, line_start, out_len, out, total, stream_off, None,
+            totals, *tail)
+        end = torch.cat([totals, stream_off]).cpu().tolist()
+        if end[1] or end[0] != total:
+            raise N.NativeError("avdb_vcf_split_write" + suffix, N.AVDB_ERANGE,
+                                f"lines of {end[0]} bytes do not fit the {total} the size pass gave")
+        cnt = {"lines": n_of, "bytes": b_of, "comments": comments, "host_lines": host_lines}
+        return SplitVcf(out[:total], [int(x) for x in end[2:]], cnt, first_other)
 
     # -- K10: CADD table and allele join ---------------------------------------
     def new_cadd_counters(self) -> torch.Tensor:

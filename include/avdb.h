@@ -1093,6 +1093,74 @@ int avdb_export_vcf_write_host(const avdb_ctx* ctx, const uint8_t* text, size_t 
                                const uint32_t* ms_len, const uint32_t* out_len, const uint8_t* row_flags, uint8_t* out,
                                size_t out_cap, uint64_t* row_off, uint64_t* totals);
 
+/* ---- K15: a whole-genome VCF split into per-chromosome texts ---------------------
+ * Replaces the per-line host code of Util/bin/split_vcf_by_chr.py (run, :29-52): `text`
+ * is a '\n'-separated slab of a VCF (n_lines as for K0, K10a and K12-K14) and the output
+ * is one blob of 26 streams back to back: the data lines of chr1.vcf ... chr22.vcf,
+ * chrX.vcf, chrY.vcf, chrM.vcf (streams 0..24, the order of the HumanChromosome enum) and
+ * the lines the reference cannot place (stream AVDB_SPLIT_OTHER).  Inside a stream the
+ * lines are in file order, each its stored bytes and a '\n'.  Header lines are the
+ * caller's to write.
+ * Line rule: a line's stored length is its length after Python's str.rstrip().  The
+ * passes strip the six ASCII whitespace bytes (space, \t, \n, \v, \f, \r).  A line whose
+ * last byte after that strip is 0x1C..0x1F or >= 0x80 is flagged AVDB_SPLIT_LINE_HOST,
+ * bit 31 of its out_len, comments included: Python strips 0x1C..0x1F too, and the bytes
+ * >= 0x80 may end a character it strips (U+0085, U+00A0, ...) or one its decode raises
+ * on.  The caller decides such a line and stores its code and its out_len (the bit
+ * cleared) before the write pass; Python's result is always a prefix of the line, so the
+ * write pass needs nothing else.  The write pass ignores the bit.
+ * A line whose first byte is '#' is a comment: no output, code AVDB_SPLIT_NONE, out_len
+ * 0.  Every other line, the empty one too, has a key: its bytes before the first '\t',
+ * or all of them.  Without a chromosome map the line's stream is c when the key is
+ * exactly the c-th of the labels 1..22, X, Y, M (`chr1`, `MT`, `01`, `x`, `1 ` and the
+ * empty key are none: the reference raises KeyError there).  With a map the key is
+ * looked up as bytes and the stream is the key's code when that is below 25.  Every
+ * other line goes to stream AVDB_SPLIT_OTHER, and counts[AVDB_SPLIT_COUNT_FIRST_OTHER] is
+ * the smallest index of such a line (~0: none).
+ * Invalid UTF-8 that does not sit at the stripped end of a line is copied verbatim,
+ * where the reference's decode raises UnicodeDecodeError.
+ *   1. avdb_vcf_split_size: per line code (u8), line_start (u64: the line's offset in
+ *      the slab; an entry of a line past the text's own count is ~0) and out_len (u32:
+ *      the stored length plus 1, 0 for a comment; bit 31: AVDB_SPLIT_LINE_HOST);
+ *      counts (AVDB_SPLIT_N_COUNTS x u64, set by the call): the lines of each stream,
+ *      the bytes of each stream, the comments, the LINE_HOST lines, first_other.
+ *   2. avdb_vcf_split_write: the destination of every line (the exclusive sum of the
+ *      out_len of the lines before it in its stream, after the streams before it) and
+ *      the copy.  stream_off (27 x u64): the start of each stream in out and, in
+ *      stream_off[26], the total.  dst_off (n_lines x u64, or NULL): each line's
+ *      destination, ~0 for a line without output.  A code that is none of 0..25 gives no
+ *      output.  totals (2 x u64): the bytes of all streams, and 1 when they exceed
+ *      out_cap.  Nothing outside [0, total) is written, and nothing at all when out_cap
+ *      is too small: the host entry returns AVDB_ERANGE then; the device entry, which
+ *      does not wait for its own scan, returns AVDB_OK and leaves totals[1] != 0.
+ * Workspace: avdb_vcf_split_workspace_size bytes, 256-byte aligned; the device entries
+ * allocate nothing per call.  The _host entries run the same per-line code on host
+ * pointers, on an avdb_ctx_create(-1, ...) context (chrom_map made on that context). */
+#define AVDB_SPLIT_N_STREAMS 26
+#define AVDB_SPLIT_OTHER 25
+#define AVDB_SPLIT_NONE 0xFFu
+#define AVDB_SPLIT_LINE_HOST 0x80000000u
+#define AVDB_SPLIT_COUNT_LINES 0        /* 26 slots: the lines of stream c */
+#define AVDB_SPLIT_COUNT_BYTES 26       /* 26 slots: the bytes of stream c */
+#define AVDB_SPLIT_COUNT_COMMENTS 52
+#define AVDB_SPLIT_COUNT_HOST_LINES 53
+#define AVDB_SPLIT_COUNT_FIRST_OTHER 54
+#define AVDB_SPLIT_N_COUNTS 55
+int avdb_vcf_split_workspace_size(size_t text_bytes, size_t n_lines, size_t* bytes);
+int avdb_vcf_split_size(avdb_ctx* ctx, const uint8_t* text, size_t text_bytes, size_t n_lines,
+                        const avdb_chrom_map* chrom_map, uint8_t* code, uint64_t* line_start, uint32_t* out_len,
+                        uint64_t* counts, void* workspace, size_t workspace_bytes, void* stream);
+int avdb_vcf_split_write(avdb_ctx* ctx, const uint8_t* text, size_t text_bytes, size_t n_lines, const uint8_t* code,
+                         const uint64_t* line_start, const uint32_t* out_len, uint8_t* out, size_t out_cap,
+                         uint64_t* stream_off, uint64_t* dst_off, uint64_t* totals, void* workspace,
+                         size_t workspace_bytes, void* stream);
+int avdb_vcf_split_size_host(const avdb_ctx* ctx, const uint8_t* text, size_t text_bytes, size_t n_lines,
+                             const avdb_chrom_map* chrom_map, uint8_t* code, uint64_t* line_start, uint32_t* out_len,
+                             uint64_t* counts);
+int avdb_vcf_split_write_host(const avdb_ctx* ctx, const uint8_t* text, size_t text_bytes, size_t n_lines,
+                              const uint8_t* code, const uint64_t* line_start, const uint32_t* out_len, uint8_t* out,
+                              size_t out_cap, uint64_t* stream_off, uint64_t* dst_off, uint64_t* totals);
+
 /* ---- K9: genome-piece sharding of VCF text --------------------------------
  * The reference runs one process per chromosome file (Load/bin/load_vcf_file.py:
  * 307-313).  One file is split over the ranks of a node by a piece plan
