@@ -5,8 +5,8 @@
 // buffer_variants: a tuple, a dict and a json.dumps per record) with two passes over
 // the export text (record_primary_key<TAB>metaseq_id<TAB>cadd_scores) on the device:
 //   size pass (avdb_cadd_update_size)
-//     (avdb_lines.hpp, shared with K10 and K12: one start per line, the marks scanned
-//      into row numbers)
+//     (avdb_lines.hpp, the front end shared with K10, K12 and K14: one start per line, the
+//      marks scanned into row numbers; rows::begin_size)
 //     k_caddupd_lines    one lane per line (lines::for_each_line: 256 lines' text staged
 //                        in LDS): the row rule, the skip, the metaseq id's four parts, the
 //                        K10 join (cadd::match_rows, the alleles read where they lie in
@@ -14,14 +14,16 @@
 //                        a mark per line
 //     k_caddupd_compact  one lane per line: a row's columns to its row number; the counts
 //   write pass (avdb_cadd_update_write)
-//     (exclusive scan of the output lengths into row_off)
-//     k_caddupd_totals   the total against the caller's capacity
-//     k_caddupd_write    one workgroup per 256 rows: each lane renders its row into the
-//                        workgroup's LDS stage (the scores rewritten from the table's own
-//                        text, caddupd::score_text), then the trip's one contiguous span
-//                        of the output is stored as aligned 8-byte words, one per lane
+//     (avdb_rows.hpp, the back end shared with K12 and K14.  rows::begin_write: the
+//      exclusive scan of the output lengths into row_off, k_row_totals: the total against
+//      the caller's capacity)
+//     k_caddupd_write    rows::write_rows, one workgroup per 256 rows: each lane renders its
+//                        row into the workgroup's LDS stage (the scores rewritten from the
+//                        table's own text, caddupd::score_text), then the trip's one
+//                        contiguous span of the output is stored as aligned 8-byte words
 // The per-line and per-row code is avdb_caddupd.hpp, shared with the _host entries.
 #include "avdb_caddupd.hpp"
+#include "avdb_rows.hpp"
 
 #include <string.h>
 
@@ -112,88 +114,31 @@ __global__ __launch_bounds__(kBlock) void k_caddupd_compact(const uint64_t* __re
   wave_add(&counts[AVDB_CADDUPD_COUNT_BAD], n_bad);
 }
 
-// row_off[n_rows] = totals[0] = the bytes of all rows; totals[1]: 1 when they exceed cap
-// (the write kernel then writes nothing)
-__global__ void k_caddupd_totals(const uint32_t* __restrict__ out_len, uint64_t* __restrict__ row_off, size_t n_rows,
-                                 uint64_t cap, uint64_t* __restrict__ totals) {
-  if (blockIdx.x || threadIdx.x) return;
-  const uint64_t t = n_rows ? row_off[n_rows - 1] + out_len[n_rows - 1] : 0ull;
-  row_off[n_rows] = t;
-  totals[0] = t;
-  totals[1] = t > cap;
-}
-
-// The write pass stores about 90 bytes per row.  A lane storing its own row to global
-// memory issues one store per byte or word with 64 different cache lines under it (what
-// bounds K5's write pass).  Here a lane renders its row into LDS, at the place the row
-// has in the trip's span of the output — the 256 rows of a trip own one contiguous span —
-// and the span then goes out as aligned 8-byte words, lane i taking the i-th: a wave's
-// store instruction covers 512 contiguous bytes.  Only the span's two edge words, shared
-// with the neighbouring trips, are stored bytewise.
+// The write pass (rows::write_rows): a lane renders its row, the scores rewritten from the
+// table's own text, into the workgroup's stage.
 __global__ __launch_bounds__(kBlock) void k_caddupd_write(const uint8_t* __restrict__ text, size_t text_bytes,
                                                           Tables T, Chrom ch, UpdCols o,
                                                           const uint64_t* __restrict__ row_off, size_t n_rows,
                                                           uint8_t* __restrict__ out,
                                                           const uint64_t* __restrict__ totals) {
   __shared__ uint64_t s_out[kUpdWriteStage / 8];
-  if (totals[1]) return;  // the capacity is too small: nothing is written
-  uint8_t* s_bytes = reinterpret_cast<uint8_t*>(s_out);
   auto tb = [&](uint64_t pos) -> uint32_t { return pos < text_bytes ? uint32_t(text[pos]) : 0u; };
-  for (size_t r0 = size_t(blockIdx.x) * kBlock; r0 < n_rows; r0 += size_t(gridDim.x) * kBlock) {
-    const uint32_t nr = n_rows - r0 < kBlock ? uint32_t(n_rows - r0) : uint32_t(kBlock);
-    const uint64_t b = row_off[r0], e = row_off[r0 + nr], b8 = b & ~7ull;
-    const bool staged = e >= b && e - b8 <= kUpdWriteStage;  // (workgroup-uniform)
-    const uint32_t t = threadIdx.x;
-    if (t < nr) {
-      const size_t r = r0 + t;
-      const uint64_t off = row_off[r];
-      const Row row{o.row_start[r], o.pk_len[r], o.kind[r], o.out_len[r], o.flags[r], o.match[r]};
-      // (off + k < off + out_len = row_off[r + 1] <= e: inside the span, and the stage)
-      if (staged) {
-        const uint32_t at = uint32_t(off - b8);
-        caddupd::render_row(row, ch, T, tb, [&](uint32_t k, uint32_t c) { s_bytes[at + k] = uint8_t(c); });
-      } else {
-        caddupd::render_row(row, ch, T, tb, [&](uint32_t k, uint32_t c) { out[off + k] = uint8_t(c); });
-      }
-    }
-    __syncthreads();
-    if (staged) {
-      for (uint64_t c = b8 + 8ull * t; c < e; c += 8ull * kBlock) {
-        const uint32_t at = uint32_t(c - b8);
-        if (c >= b && c + 8 <= e) {
-          *reinterpret_cast<uint64_t*>(out + c) = s_out[at / 8];
-        } else {
-          const uint64_t lo = c > b ? c : b, hi = c + 8 < e ? c + 8 : e;
-          for (uint64_t p = lo; p < hi; ++p) out[p] = s_bytes[uint32_t(p - b8)];
-        }
-      }
-    }
-    __syncthreads();  // the stage is reused by the next trip
-  }
+  rows::write_rows<kUpdWriteStage>(
+      row_off, n_rows, out, totals, s_out,
+      [&](size_t r) { return Row{o.row_start[r], o.pk_len[r], o.kind[r], o.out_len[r], o.flags[r], o.match[r]}; },
+      [&](const Row& row, auto put) { caddupd::render_row(row, ch, T, tb, put); });
 }
 
 }  // namespace avdb
 
 using namespace avdb;
 
-// workspace: lines::Layout | line info | scan temp
-struct UpdLayout : lines::Layout {
-  size_t info, total;
-};
-static UpdLayout upd_layout(size_t n_lines) {
-  UpdLayout L{lines::layout(n_lines)};
-  L.info = L.next;
-  L.scan = L.info + lines::pad256(16 * n_lines);
-  L.scan_bytes = lines::pad256(scan::workspace_bytes(n_lines + 1));
-  L.total = L.scan + L.scan_bytes;
-  return L;
-}
+// workspace: rows::Layout with 16 bytes of info per line
+static rows::Layout upd_layout(size_t n_lines) { return rows::layout(n_lines, 16); }
 
 extern "C" int avdb_cadd_update_workspace_size(size_t text_bytes, size_t n_lines, size_t* bytes) {
   (void)text_bytes;
-  if (!bytes) return AVDB_EINVAL;
-  *bytes = upd_layout(n_lines).total;
-  return AVDB_OK;
+  return rows::workspace_size(upd_layout(n_lines).total, bytes);
 }
 
 // the arguments both passes share: the tables and the chromosome text
@@ -224,12 +169,9 @@ static const char* write_args_error(const uint8_t* text, size_t text_bytes, size
                                     const UpdCols& o, const uint8_t* out, size_t out_cap, const uint64_t* row_off,
                                     const uint64_t* totals) {
   if (!totals || !row_off) return "null argument";
-  if (text_bytes && !text) return "null text";
-  if (n_rows > n_lines || n_lines > text_bytes || n_lines >= 0x7FFFFFFFull) return "n_rows / n_lines out of range";
+  if (const char* err = rows::text_rows_error(text, text_bytes, n_lines, n_rows)) return err;
   if (n_rows && (!o.row_start || !o.pk_len || !o.kind || !o.match || !o.out_len || !o.flags)) return "null row array";
-  if (out_cap && !out) return "null output";
-  if (reinterpret_cast<uintptr_t>(out) % 8) return "the output must be 8-byte aligned";
-  return nullptr;
+  return rows::out_error(out, out_cap);
 }
 
 extern "C" int avdb_cadd_update_size(avdb_ctx* ctx, const uint8_t* text, size_t text_bytes, size_t n_lines,
@@ -247,12 +189,11 @@ extern "C" int avdb_cadd_update_size(avdb_ctx* ctx, const uint8_t* text, size_t 
     avdb_set_error("avdb_cadd_update_size: %s", err);
     return AVDB_EINVAL;
   }
-  const UpdLayout L = upd_layout(n_lines);
-  if (int e = n_lines ? lines::workspace_error("avdb_cadd_update_size", L.total, workspace, workspace_bytes) : 0)
-    return e;
-  AVDB_HIP_TRY(hipSetDevice(ctx->device));
+  const rows::Layout L = upd_layout(n_lines);
   hipStream_t s = static_cast<hipStream_t>(stream);
-  AVDB_HIP_TRY(hipMemsetAsync(counts, 0, 8 * AVDB_CADDUPD_N_COUNTS, s));
+  if (int e = rows::begin_size("avdb_cadd_update_size", ctx, L.total, n_lines, workspace, workspace_bytes, counts,
+                               AVDB_CADDUPD_N_COUNTS, s))
+    return e;
   if (n_lines == 0) return AVDB_OK;
   char* w = static_cast<char*>(workspace);
   auto* info = reinterpret_cast<u32x4*>(w + L.info);
@@ -288,16 +229,10 @@ extern "C" int avdb_cadd_update_write(avdb_ctx* ctx, const uint8_t* text, size_t
     avdb_set_error("avdb_cadd_update_write: %s", err);
     return AVDB_EINVAL;
   }
-  const UpdLayout L = upd_layout(n_lines);
-  if (int e = n_lines ? lines::workspace_error("avdb_cadd_update_write", L.total, workspace, workspace_bytes) : 0)
-    return e;
-  AVDB_HIP_TRY(hipSetDevice(ctx->device));
   hipStream_t s = static_cast<hipStream_t>(stream);
-  char* w = static_cast<char*>(workspace);
-  if (n_rows)
-    if (int e = scan::exclusive_u64(out_len, row_off, n_rows, w + L.scan, L.scan_bytes, s)) return e;
-  hipLaunchKernelGGL(k_caddupd_totals, dim3(1), dim3(kWave), 0, s, out_len, row_off, n_rows, uint64_t(out_cap), totals);
-  AVDB_LAUNCH_CHECK("k_caddupd_totals");
+  if (int e = rows::begin_write("avdb_cadd_update_write", ctx, upd_layout(n_lines), n_lines, workspace, workspace_bytes,
+                                out_len, n_rows, out_cap, row_off, totals, s))
+    return e;
   if (n_rows == 0) return AVDB_OK;
   hipLaunchKernelGGL(k_caddupd_write, dim3(stream_grid(n_rows, kBlock, 2048)), dim3(kBlock), 0, s, text, text_bytes, T,
                      ch, o, row_off, n_rows, out, totals);
@@ -369,18 +304,7 @@ extern "C" int avdb_cadd_update_write_host(const avdb_ctx* ctx, const uint8_t* t
     avdb_set_error("avdb_cadd_update_write_host: %s", err);
     return AVDB_EINVAL;
   }
-  uint64_t t = 0;
-  for (size_t r = 0; r < n_rows; ++r) {
-    row_off[r] = t;
-    t += out_len[r];
-  }
-  row_off[n_rows] = t;
-  totals[0] = t;
-  totals[1] = t > out_cap;
-  if (totals[1]) {
-    avdb_set_error("avdb_cadd_update_write_host: output of %llu bytes required", (unsigned long long)t);
-    return AVDB_ERANGE;
-  }
+  if (int e = rows::host_row_offsets("avdb_cadd_update_write_host", out_len, n_rows, out_cap, row_off, totals)) return e;
   auto tb = [&](uint64_t pos) -> uint32_t { return pos < text_bytes ? uint32_t(text[pos]) : 0u; };
   for (size_t r = 0; r < n_rows; ++r) {
     const Row row{row_start[r], pk_len[r], kind[r], out_len[r], row_flags[r], match[r]};

@@ -5,13 +5,15 @@
 // (a split, a one-entry list of a dict, two encodes, a repr and three joins per
 // exported row) with two passes over the export text on the device:
 //   size pass (avdb_existing_size)
-//     (avdb_lines.hpp, shared with K10: one start per line, the marks scanned into row numbers)
+//     (avdb_lines.hpp, the front end shared with K10, K13 and K14: one start per line, the marks
+//      scanned into row numbers; rows::begin_size)
 //     k_exist_lines    one lane per line (lines::for_each_line: 256 lines' text staged
 //                      in LDS): from_tsv's row rule, the three field lengths, the row's
 //                      flags, the lone '\r' count; 16 bytes of info and a mark per line
 //     k_exist_compact  one lane per line: a row's lengths, flags and line start to
 //                      its row number; the counts
-//   write pass (avdb_existing_write)
+//   write pass (avdb_existing_write; the workspace, the argument checks and the host entry's
+//   offsets are avdb_rows.hpp's, the back end shared with K13 and K14)
 //     (exclusive scan of the three length arrays into the three offset arrays)
 //     k_exist_totals   the blob totals against the caller's caps
 //     k_exist_write    one workgroup per 128 rows: their text staged in LDS, then
@@ -19,6 +21,7 @@
 //                      one word per lane (see below)
 // The per-line and per-row code is avdb_existing.hpp, shared with the _host entries.
 #include "avdb_existing.hpp"
+#include "avdb_rows.hpp"
 
 #include <string.h>
 
@@ -216,25 +219,12 @@ __global__ __launch_bounds__(kBlock) void k_exist_write(const uint8_t* __restric
 
 using namespace avdb;
 
-// workspace: lines::Layout | line info | scan temp
-struct ExistLayout : lines::Layout {
-  size_t info, total;
-};
-static ExistLayout exist_layout(size_t n_lines) {
-  ExistLayout L{lines::layout(n_lines)};
-  L.info = L.next;
-  L.scan = L.info + lines::pad256(16 * n_lines);
-  const size_t a = scan::workspace_bytes(n_lines + 1), b = scan::workspace_bytes(n_lines, 3);
-  L.scan_bytes = lines::pad256(a > b ? a : b);
-  L.total = L.scan + L.scan_bytes;
-  return L;
-}
+// workspace: rows::Layout with 16 bytes of info per line; the write pass scans three length arrays
+static rows::Layout exist_layout(size_t n_lines) { return rows::layout(n_lines, 16, 0, 3); }
 
 extern "C" int avdb_existing_workspace_size(size_t text_bytes, size_t n_lines, size_t* bytes) {
   (void)text_bytes;
-  if (!bytes) return AVDB_EINVAL;
-  *bytes = exist_layout(n_lines).total;
-  return AVDB_OK;
+  return rows::workspace_size(exist_layout(n_lines).total, bytes);
 }
 
 static const char* size_args_error(const void* ctx, const uint8_t* text, size_t text_bytes, size_t n_lines,
@@ -251,8 +241,7 @@ static const char* write_args_error(const void* ctx, const uint8_t* text, size_t
                                     const uint32_t* frag_len, const uint8_t* flags, const uint64_t* row_off,
                                     const ExistOut& o, const uint64_t* totals) {
   if (!ctx || !totals || !o.off[0] || !o.off[1] || !o.off[2]) return "null argument";
-  if (text_bytes && !text) return "null text";
-  if (n_rows > n_lines || n_lines > text_bytes || n_lines >= 0x7FFFFFFFull) return "n_rows / n_lines out of range";
+  if (const char* err = rows::text_rows_error(text, text_bytes, n_lines, n_rows)) return err;
   if (n_rows && (!key_len || !pk_len || !frag_len || !flags || !row_off)) return "null row array";
   for (int a = 0; a < 3; ++a) {
     if (o.cap[a] && !o.out[a]) return "null blob";
@@ -270,11 +259,11 @@ extern "C" int avdb_existing_size(avdb_ctx* ctx, const uint8_t* text, size_t tex
     avdb_set_error("avdb_existing_size: %s", err);
     return AVDB_EINVAL;
   }
-  const ExistLayout L = exist_layout(n_lines);
-  if (int e = n_lines ? lines::workspace_error("avdb_existing_size", L.total, workspace, workspace_bytes) : 0) return e;
-  AVDB_HIP_TRY(hipSetDevice(ctx->device));
+  const rows::Layout L = exist_layout(n_lines);
   hipStream_t s = static_cast<hipStream_t>(stream);
-  AVDB_HIP_TRY(hipMemsetAsync(counts, 0, 8 * AVDB_EXIST_N_COUNTS, s));
+  if (int e = rows::begin_size("avdb_existing_size", ctx, L.total, n_lines, workspace, workspace_bytes, counts,
+                               AVDB_EXIST_N_COUNTS, s))
+    return e;
   if (n_lines == 0) return AVDB_OK;
   char* w = static_cast<char*>(workspace);
   auto* info = reinterpret_cast<u32x4*>(w + L.info);
@@ -305,7 +294,7 @@ extern "C" int avdb_existing_write(avdb_ctx* ctx, const uint8_t* text, size_t te
     avdb_set_error("avdb_existing_write: %s", err);
     return AVDB_EINVAL;
   }
-  const ExistLayout L = exist_layout(n_lines);
+  const rows::Layout L = exist_layout(n_lines);
   if (int e = n_lines ? lines::workspace_error("avdb_existing_write", L.total, workspace, workspace_bytes) : 0) return e;
   AVDB_HIP_TRY(hipSetDevice(ctx->device));
   hipStream_t s = static_cast<hipStream_t>(stream);
@@ -374,16 +363,7 @@ extern "C" int avdb_existing_write_host(const avdb_ctx* ctx, const uint8_t* text
     return AVDB_EINVAL;
   }
   totals[3] = 0;
-  for (int a = 0; a < 3; ++a) {
-    uint64_t t = 0;
-    for (size_t r = 0; r < n_rows; ++r) {
-      o.off[a][r] = t;
-      t += o.len[a][r];
-    }
-    o.off[a][n_rows] = t;
-    totals[a] = t;
-    totals[3] += t > o.cap[a];
-  }
+  for (int a = 0; a < 3; ++a) totals[3] += rows::host_offsets(o.len[a], n_rows, o.cap[a], o.off[a], &totals[a]);
   if (totals[3]) {
     avdb_set_error("avdb_existing_write_host: blobs of %llu / %llu / %llu bytes required",
                    (unsigned long long)totals[0], (unsigned long long)totals[1], (unsigned long long)totals[2]);

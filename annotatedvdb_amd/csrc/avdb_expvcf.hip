@@ -5,20 +5,23 @@
 // eight-field print per record) with two passes over the export text
 // (record_primary_key<TAB>metaseq_id<TAB>row_algorithm_id) on the device:
 //   size pass (avdb_export_vcf_size)
-//     (avdb_lines.hpp, shared with K10, K12 and K13: one start per line; the two marks of a
-//      line, valid and invalid, share one 64-bit word, so one scan numbers both lists)
+//     (avdb_lines.hpp, the front end shared with K10, K12 and K13: one start per line; the two
+//      marks of a line, valid and invalid, share one 64-bit word, so one scan numbers both
+//      lists; rows::begin_size)
 //     k_expvcf_lines     one lane per line (lines::for_each_line: 256 lines' text staged in
 //                        LDS): the row rule, the class, the lengths, K6's hash of the key;
 //                        16 bytes of info, the hash and a mark per line
 //     k_expvcf_compact   one lane per line: a row's columns to its number in its list; the counts
 //   write pass (avdb_export_vcf_write, once per stream over its own row list)
-//     (exclusive scan of the output lengths into row_off)
-//     k_expvcf_totals    the total against the caller's capacity
-//     k_expvcf_write     one workgroup per 256 rows: each lane renders its row into the
-//                        workgroup's LDS stage, then the trip's one contiguous span of the
-//                        output is stored as aligned 8-byte words, one per lane
+//     (avdb_rows.hpp, the back end shared with K12 and K13.  rows::begin_write: the exclusive
+//      scan of the output lengths into row_off, k_row_totals: the total against the caller's
+//      capacity)
+//     k_expvcf_write     rows::write_rows, one workgroup per 256 rows: each lane renders its
+//                        row into the workgroup's LDS stage, then the trip's one contiguous
+//                        span of the output is stored as aligned 8-byte words, one per lane
 // The per-line and per-row code is avdb_expvcf.hpp, shared with the _host entries.
 #include "avdb_expvcf.hpp"
+#include "avdb_rows.hpp"
 
 #include <string.h>
 
@@ -115,22 +118,8 @@ __global__ __launch_bounds__(kBlock) void k_expvcf_compact(const uint64_t* __res
   wave_add(&counts[AVDB_EXPVCF_COUNT_BAD], n_bad);
 }
 
-// row_off[n_rows] = totals[0] = the bytes of all rows; totals[1]: 1 when they exceed cap
-// (the write kernel then writes nothing)
-__global__ void k_expvcf_totals(const uint32_t* __restrict__ out_len, uint64_t* __restrict__ row_off, size_t n_rows,
-                                uint64_t cap, uint64_t* __restrict__ totals) {
-  if (blockIdx.x || threadIdx.x) return;
-  const uint64_t t = n_rows ? row_off[n_rows - 1] + out_len[n_rows - 1] : 0ull;
-  row_off[n_rows] = t;
-  totals[0] = t;
-  totals[1] = t > cap;
-}
-
-// The write pass of either stream, as K13's (k_caddupd_write): a lane renders its row into
-// LDS at the place the row has in the trip's span of the output, and the span goes out as
-// aligned 8-byte words, lane i taking the i-th; the span's two edge words, shared with the
-// neighbouring trips, are stored bytewise.  kInvalidStream: the rows are the invalid
-// file's (ms_len and flags are not read).
+// The write pass of either stream (rows::write_rows).  kInvalidStream: the rows are the
+// invalid file's (ms_len and flags are not read).
 template <bool kInvalidStream>
 __global__ __launch_bounds__(kBlock) void k_expvcf_write(const uint8_t* __restrict__ text, size_t text_bytes,
                                                          const uint64_t* __restrict__ row_start,
@@ -142,75 +131,35 @@ __global__ __launch_bounds__(kBlock) void k_expvcf_write(const uint8_t* __restri
                                                          uint8_t* __restrict__ out,
                                                          const uint64_t* __restrict__ totals) {
   __shared__ uint64_t s_out[kVcfWriteStage / 8];
-  if (totals[1]) return;  // the capacity is too small: nothing is written
-  uint8_t* s_bytes = reinterpret_cast<uint8_t*>(s_out);
   auto tb = [&](uint64_t pos) -> uint32_t { return pos < text_bytes ? uint32_t(text[pos]) : 0u; };
-  for (size_t r0 = size_t(blockIdx.x) * kBlock; r0 < n_rows; r0 += size_t(gridDim.x) * kBlock) {
-    const uint32_t nr = n_rows - r0 < kBlock ? uint32_t(n_rows - r0) : uint32_t(kBlock);
-    const uint64_t b = row_off[r0], e = row_off[r0 + nr], b8 = b & ~7ull;
-    const bool staged = e >= b && e - b8 <= kVcfWriteStage;  // (workgroup-uniform)
-    const uint32_t t = threadIdx.x;
-    if (t < nr) {
-      const size_t r = r0 + t;
-      const uint64_t off = row_off[r];
-      Row row{row_start[r], pk_len[r], 0, out_len[r], 0};
-      if constexpr (!kInvalidStream) {
-        row.ms_len = ms_len[r];
-        row.flags = flags[r];
-      }
-      // (off + k < off + out_len = row_off[r + 1] <= e: inside the span, and the stage)
-      auto render = [&](auto put) {
+  rows::write_rows<kVcfWriteStage>(
+      row_off, n_rows, out, totals, s_out,
+      [&](size_t r) {
+        Row row{row_start[r], pk_len[r], 0, out_len[r], 0};
+        if constexpr (!kInvalidStream) {
+          row.ms_len = ms_len[r];
+          row.flags = flags[r];
+        }
+        return row;
+      },
+      [&](const Row& row, auto put) {
         if constexpr (kInvalidStream)
           expvcf::render_invalid_row(row, text_bytes, tb, put);
         else
           expvcf::render_vcf_row(row, tb, put);
-      };
-      if (staged) {
-        const uint32_t at = uint32_t(off - b8);
-        render([&](uint32_t k, uint32_t c) { s_bytes[at + k] = uint8_t(c); });
-      } else {
-        render([&](uint32_t k, uint32_t c) { out[off + k] = uint8_t(c); });
-      }
-    }
-    __syncthreads();
-    if (staged) {
-      for (uint64_t c = b8 + 8ull * t; c < e; c += 8ull * kBlock) {
-        const uint32_t at = uint32_t(c - b8);
-        if (c >= b && c + 8 <= e) {
-          *reinterpret_cast<uint64_t*>(out + c) = s_out[at / 8];
-        } else {
-          const uint64_t lo = c > b ? c : b, hi = c + 8 < e ? c + 8 : e;
-          for (uint64_t p = lo; p < hi; ++p) out[p] = s_bytes[uint32_t(p - b8)];
-        }
-      }
-    }
-    __syncthreads();  // the stage is reused by the next trip
-  }
+      });
 }
 
 }  // namespace avdb
 
 using namespace avdb;
 
-// workspace: lines::Layout | line info | line hashes | scan temp
-struct VcfLayout : lines::Layout {
-  size_t info, hash, total;
-};
-static VcfLayout vcf_layout(size_t n_lines) {
-  VcfLayout L{lines::layout(n_lines)};
-  L.info = L.next;
-  L.hash = L.info + lines::pad256(16 * n_lines);
-  L.scan = L.hash + lines::pad256(8 * n_lines);
-  L.scan_bytes = lines::pad256(scan::workspace_bytes(n_lines + 1));
-  L.total = L.scan + L.scan_bytes;
-  return L;
-}
+// workspace: rows::Layout with 16 bytes of info and the 8 of the key's hash per line
+static rows::Layout vcf_layout(size_t n_lines) { return rows::layout(n_lines, 16, 8); }
 
 extern "C" int avdb_export_vcf_workspace_size(size_t text_bytes, size_t n_lines, size_t* bytes) {
   (void)text_bytes;
-  if (!bytes) return AVDB_EINVAL;
-  *bytes = vcf_layout(n_lines).total;
-  return AVDB_OK;
+  return rows::workspace_size(vcf_layout(n_lines).total, bytes);
 }
 
 static const char* size_args_error(const void* ctx, const uint8_t* text, size_t text_bytes, size_t n_lines,
@@ -232,13 +181,10 @@ static const char* write_args_error(const void* ctx, const uint8_t* text, size_t
   if (!ctx) return "null context";
   if (!totals || !row_off) return "null argument";
   if (which != AVDB_EXPVCF_STREAM_VCF && which != AVDB_EXPVCF_STREAM_INVALID) return "no such stream";
-  if (text_bytes && !text) return "null text";
-  if (n_rows > n_lines || n_lines > text_bytes || n_lines >= 0x7FFFFFFFull) return "n_rows / n_lines out of range";
+  if (const char* err = rows::text_rows_error(text, text_bytes, n_lines, n_rows)) return err;
   if (n_rows && (!row_start || !pk_len || !out_len)) return "null row array";
   if (n_rows && which == AVDB_EXPVCF_STREAM_VCF && (!ms_len || !row_flags)) return "null row array";
-  if (out_cap && !out) return "null output";
-  if (reinterpret_cast<uintptr_t>(out) % 8) return "the output must be 8-byte aligned";
-  return nullptr;
+  return rows::out_error(out, out_cap);
 }
 
 extern "C" int avdb_export_vcf_size(avdb_ctx* ctx, const uint8_t* text, size_t text_bytes, size_t n_lines,
@@ -252,16 +198,15 @@ extern "C" int avdb_export_vcf_size(avdb_ctx* ctx, const uint8_t* text, size_t t
     avdb_set_error("avdb_export_vcf_size: %s", err);
     return AVDB_EINVAL;
   }
-  const VcfLayout L = vcf_layout(n_lines);
-  if (int e = n_lines ? lines::workspace_error("avdb_export_vcf_size", L.total, workspace, workspace_bytes) : 0)
-    return e;
-  AVDB_HIP_TRY(hipSetDevice(ctx->device));
+  const rows::Layout L = vcf_layout(n_lines);
   hipStream_t s = static_cast<hipStream_t>(stream);
-  AVDB_HIP_TRY(hipMemsetAsync(counts, 0, 8 * AVDB_EXPVCF_N_COUNTS, s));
+  if (int e = rows::begin_size("avdb_export_vcf_size", ctx, L.total, n_lines, workspace, workspace_bytes, counts,
+                               AVDB_EXPVCF_N_COUNTS, s))
+    return e;
   if (n_lines == 0) return AVDB_OK;
   char* w = static_cast<char*>(workspace);
   auto* info = reinterpret_cast<u32x4*>(w + L.info);
-  auto* hash = reinterpret_cast<uint64_t*>(w + L.hash);
+  auto* hash = reinterpret_cast<uint64_t*>(w + L.extra);
   auto* cnt = reinterpret_cast<unsigned long long*>(counts);
   const unsigned grid = stream_grid(n_lines, kBlock, 4096);
   auto mark = [&](const uint64_t* starts, uint64_t* marks) {
@@ -285,16 +230,10 @@ extern "C" int avdb_export_vcf_write(avdb_ctx* ctx, const uint8_t* text, size_t 
     avdb_set_error("avdb_export_vcf_write: %s", err);
     return AVDB_EINVAL;
   }
-  const VcfLayout L = vcf_layout(n_lines);
-  if (int e = n_lines ? lines::workspace_error("avdb_export_vcf_write", L.total, workspace, workspace_bytes) : 0)
-    return e;
-  AVDB_HIP_TRY(hipSetDevice(ctx->device));
   hipStream_t s = static_cast<hipStream_t>(stream);
-  char* w = static_cast<char*>(workspace);
-  if (n_rows)
-    if (int e = scan::exclusive_u64(out_len, row_off, n_rows, w + L.scan, L.scan_bytes, s)) return e;
-  hipLaunchKernelGGL(k_expvcf_totals, dim3(1), dim3(kWave), 0, s, out_len, row_off, n_rows, uint64_t(out_cap), totals);
-  AVDB_LAUNCH_CHECK("k_expvcf_totals");
+  if (int e = rows::begin_write("avdb_export_vcf_write", ctx, vcf_layout(n_lines), n_lines, workspace, workspace_bytes,
+                                out_len, n_rows, out_cap, row_off, totals, s))
+    return e;
   if (n_rows == 0) return AVDB_OK;
   const dim3 grid(stream_grid(n_rows, kBlock, 2048));
   if (which == AVDB_EXPVCF_STREAM_VCF)
@@ -363,18 +302,7 @@ extern "C" int avdb_export_vcf_write_host(const avdb_ctx* ctx, const uint8_t* te
     avdb_set_error("avdb_export_vcf_write_host: %s", err);
     return AVDB_EINVAL;
   }
-  uint64_t t = 0;
-  for (size_t r = 0; r < n_rows; ++r) {
-    row_off[r] = t;
-    t += out_len[r];
-  }
-  row_off[n_rows] = t;
-  totals[0] = t;
-  totals[1] = t > out_cap;
-  if (totals[1]) {
-    avdb_set_error("avdb_export_vcf_write_host: output of %llu bytes required", (unsigned long long)t);
-    return AVDB_ERANGE;
-  }
+  if (int e = rows::host_row_offsets("avdb_export_vcf_write_host", out_len, n_rows, out_cap, row_off, totals)) return e;
   auto tb = [&](uint64_t pos) -> uint32_t { return pos < text_bytes ? uint32_t(text[pos]) : 0u; };
   for (size_t r = 0; r < n_rows; ++r) {
     const uint64_t off = row_off[r];

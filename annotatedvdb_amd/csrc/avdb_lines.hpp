@@ -1,6 +1,9 @@
-// The front end of the table builds over a '\n'-separated text slab (K10, avdb_cadd.hip; K12,
-// avdb_existing.hip): one start per line, the lines walked 256 per workgroup trip with their text
-// staged in LDS, a mark per line scanned into row numbers.  Compiled for both sides, as avdb_cadd.hpp is.
+// The front end of the passes over a '\n'-separated text slab (K10, avdb_cadd.hip; K12,
+// avdb_existing.hip; K13, avdb_caddupd.hip; K14, avdb_expvcf.hip; the line spans also K15,
+// avdb_splitvcf.hip): one start per line, the lines walked 256 per workgroup trip with their text
+// staged in LDS, a mark per line scanned into row numbers.  What follows the row numbers in the
+// two-pass exports (workspace, prologues, offsets and totals, the staged row writer) is
+// avdb_rows.hpp.  Compiled for both sides, as avdb_cadd.hpp is.
 #pragma once
 
 #include "avdb_scan.hpp"

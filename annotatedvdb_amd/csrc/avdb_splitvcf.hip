@@ -3,7 +3,8 @@
 // Replaces the per-line Python of Util/bin/split_vcf_by_chr.py (run: a gzip read, a decode,
 // an rstrip, a split, a dict lookup and a print per line on one host thread) with a stable
 // 26-way partition of the slab's lines on the device:
-//   size pass (avdb_vcf_split_size)
+//   size pass (avdb_vcf_split_size; rows::begin_size, the prologue shared with K12, K13 and K14:
+//   avdb_rows.hpp)
 //     (K0's count and line-starts passes write the caller's line_start)
 //     k_split_lines    one lane per line, 256 lines' text staged in LDS: the stored length
 //                      (rstrip), the comment test, the key's stream (exact label, or the
@@ -21,6 +22,7 @@
 //                      64 consecutive bytes per store
 // The per-line code is avdb_splitvcf.hpp, shared with the _host entries.
 #include "avdb_splitvcf.hpp"
+#include "avdb_rows.hpp"
 
 #include <string.h>
 
@@ -274,9 +276,7 @@ static SplitLayout split_layout(size_t n_lines) {
 
 extern "C" int avdb_vcf_split_workspace_size(size_t text_bytes, size_t n_lines, size_t* bytes) {
   (void)text_bytes;
-  if (!bytes) return AVDB_EINVAL;
-  *bytes = split_layout(n_lines).total;
-  return AVDB_OK;
+  return rows::workspace_size(split_layout(n_lines).total, bytes);
 }
 
 static const char* size_args_error(const void* ctx, const uint8_t* text, size_t text_bytes, size_t n_lines,
@@ -314,10 +314,10 @@ extern "C" int avdb_vcf_split_size(avdb_ctx* ctx, const uint8_t* text, size_t te
     return AVDB_EINVAL;
   }
   const SplitLayout L = split_layout(n_lines);
-  if (int e = n_lines ? lines::workspace_error("avdb_vcf_split_size", L.total, workspace, workspace_bytes) : 0) return e;
-  AVDB_HIP_TRY(hipSetDevice(ctx->device));
   hipStream_t s = static_cast<hipStream_t>(stream);
-  AVDB_HIP_TRY(hipMemsetAsync(counts, 0, 8 * AVDB_SPLIT_COUNT_FIRST_OTHER, s));
+  if (int e = rows::begin_size("avdb_vcf_split_size", ctx, L.total, n_lines, workspace, workspace_bytes, counts,
+                               AVDB_SPLIT_COUNT_FIRST_OTHER, s))
+    return e;
   AVDB_HIP_TRY(hipMemsetAsync(counts + AVDB_SPLIT_COUNT_FIRST_OTHER, 0xFF, 8, s));
   if (n_lines == 0) return AVDB_OK;
   AVDB_HIP_TRY(hipMemsetAsync(line_start, 0xFF, 8 * n_lines, s));

@@ -31,6 +31,7 @@ import numpy as np
 import torch
 
 from . import _native as N
+from . import slab_passes
 from .chromosomes import CHROM_NAMES, N_CHROM, length_table
 
 
@@ -134,7 +135,6 @@ class CaddUpdateRows:
 
 VCF_EXPORT_HEADER = b"#CHRM\tPOS\tID\tREF\tALT\tQUAL\tFILTER\tINFO\n"  # (sic) export_variant2vcf.py:26
 
-_FILE_SALT = -7046029254386353131  # 0x9E3779B97F4A7C15 as int64: folds a row's file number into its key hash (K14)
 
 
 @dataclass
@@ -1463,62 +1463,7 @@ class Engine:
         their two fields fetched and rendered here, and copied into their spans after
         the write pass.  On a host-only engine the library's host entries run the same
         per-line code."""
-        text = self._as_text(text)
-        nb = text.numel()
-        n_lines = self._count_lines(text)
-        m = max(1, n_lines)
-        key_len, pk_len, frag_len = (self.empty(m, torch.int32) for _ in range(3))
-        flags = self.empty(m, torch.uint8)
-        row_off = self.empty(m, torch.int64)
-        counts = self.empty(N.EXIST_N_COUNTS, torch.int64)
-        tp = text if nb else None
-        if self.host_only:
-            run, suffix, tail = self._call, "_host", ()
-        else:
-            ws = self.scratch("existing_build", N.size("avdb_existing_workspace_size", nb, n_lines))
-            run, suffix, tail = self._launch, "", (ws, ws.numel())
-        run("avdb_existing_size" + suffix, tp, nb, n_lines, existing_contig_mask(contigs), key_len, pk_len, frag_len,
-            flags, row_off, counts, *tail)
-        cnt = dict(zip(N.EXIST_COUNTS, (int(x) for x in counts.cpu().numpy().astype(np.uint64))))
-        if cnt["lone_cr"]:
-            raise ValueError(f"{cnt['lone_cr']} carriage return(s) in the export that no newline follows: Python's "
-                             "text mode ends a line there and the device build does not; load this export with "
-                             "ExistingVariants.from_tsv (--existingHost)")
-        n = cnt["rows"]
-        frag_bytes = cnt["frag_bytes"]
-        host_rows = rendered = None
-        if cnt["frag_host"]:
-            # the rows repr() escapes in: their pk and bin bytes ("pk<TAB>bin") to the host
-            host_rows = torch.nonzero(flags[:n] & N.EXIST_FRAG_HOST).flatten()
-            kl, pl = key_len[host_rows].long(), pk_len[host_rows].long()
-            fl = frag_len[host_rows].long()
-            span = fl - 36 + 1  # len(pk) + 1 + len(bin): the fixed text of a fragment is 36 bytes
-            raw = text[self._spans(row_off[host_rows] + kl + 1, span)].cpu().numpy().tobytes()
-            out, new_len, at = [], [], 0
-            for p, s in zip(pl.tolist(), span.tolist()):
-                pk, bin_ = raw[at:at + p], raw[at + p + 1:at + s]
-                at += s
-                out.append(repr({"primary_key": pk.decode("utf-8"), "bin_index": bin_.decode("utf-8")}).encode("utf-8"))
-                new_len.append(len(out[-1]))
-            new_len = torch.tensor(new_len, dtype=torch.int64)
-            frag_bytes += int(new_len.sum()) - int(fl.sum())
-            frag_len[host_rows] = new_len.to(torch.int32).to(self.device)
-            rendered = (torch.from_numpy(np.frombuffer(b"".join(out), dtype=np.uint8).copy()).to(self.device),
-                        new_len.to(self.device))
-        keys = self.empty(max(1, cnt["key_bytes"]), torch.uint8)
-        pks = self.empty(max(1, cnt["pk_bytes"]), torch.uint8)
-        frag = self.empty(max(1, frag_bytes), torch.uint8)
-        key_off, pk_off, frag_off = (self.empty(n + 1, torch.int64) for _ in range(3))
-        totals = self.empty(4, torch.int64)
-        run("avdb_existing_write" + suffix, tp, nb, n_lines, n, key_len, pk_len, frag_len, flags, row_off, keys,
-            cnt["key_bytes"], key_off, pks, cnt["pk_bytes"], pk_off, frag, frag_bytes, frag_off, totals, *tail)
-        if rendered is not None:
-            frag[self._spans(frag_off[host_rows], rendered[1])] = rendered[0]
-        tot = totals.cpu().tolist()
-        if tot[3] or tot[:3] != [cnt["key_bytes"], cnt["pk_bytes"], frag_bytes]:
-            raise N.NativeError("avdb_existing_write" + suffix, N.AVDB_ERANGE,
-                                f"blob totals {tot[:3]} do not fit the sizes the size pass gave")
-        return ExistingColumns(n, keys, key_off, pks, pk_off, frag, frag_off, flags[:n], cnt)
+        return slab_passes.existing_table_build(self, text, contigs)
 
     # -- K13: CADD update rows from an export -------------------------------------
     def cadd_update_rows(self, text, snv, indel, chromosome=None, skip_existing: bool = True,
@@ -1539,95 +1484,7 @@ class Engine:
         digits, a table score the device does not parse) are rendered here with
         ``buffer_variants`` itself and copied into their spans after the write pass.
         On a host-only engine the library's host entries run the same per-line code."""
-        from .cadd import CADDUpdater, CaddTable
-        tabs = [t if t is None or isinstance(t, CaddTable) else CaddTable(t, self) for t in (snv, indel)]
-        for t in tabs:
-            if t is not None and t.cols.text.device != self.device:
-                raise ValueError("CADD table lives on another device than this engine")
-        views = [t.cols.view() if t is not None else None for t in tabs]
-        vp = [ctypes.byref(v) if v is not None else None for v in views]
-        chrom = None
-        if chromosome is not None:
-            label = str(chromosome).replace("chr", "")  # set_chromosome, then buffer_update_values' prefix
-            chrom = (label if "chr" in label else "chr" + label).encode("utf-8")
-            if not 0 < len(chrom) <= N.CADDUPD_CHROM_MAX:
-                raise ValueError(f"chromosome text of {len(chrom)} bytes (1 .. {N.CADDUPD_CHROM_MAX} taken)")
-        shared = (*vp, chrom, len(chrom) if chrom else 0)
-        text = self._as_text(text)
-        nb = text.numel()
-        n_lines = self._count_lines(text)
-        m = max(1, n_lines)
-        row_start = self.empty(m, torch.int64)
-        pk_len, out_len = self.empty(m, torch.int32), self.empty(m, torch.int32)
-        match = self.empty(m, torch.int32)
-        kind, flags = self.empty(m, torch.uint8), self.empty(m, torch.uint8)
-        counts = self.empty(N.CADDUPD_N_COUNTS, torch.int64)
-        tp = text if nb else None
-        if self.host_only:
-            run, suffix, tail = self._call, "_host", ()
-        else:
-            ws = self.scratch("cadd_update", N.size("avdb_cadd_update_workspace_size", nb, n_lines))
-            run, suffix, tail = self._launch, "", (ws, ws.numel())
-        run("avdb_cadd_update_size" + suffix, tp, nb, n_lines, *shared, existing_contig_mask(contigs),
-            N.CADDUPD_SKIP_EXISTING if skip_existing else 0, row_start, pk_len, kind, match, out_len, flags, counts,
-            *tail)
-        cnt = dict(zip(N.CADDUPD_COUNTS, (int(x) for x in counts.cpu().numpy().astype(np.uint64))))
-        if cnt["lone_cr"]:
-            raise ValueError(f"{cnt['lone_cr']} carriage return(s) in the export that no newline follows: Python's "
-                             "text mode ends a line there and the device pass does not; feed this export to "
-                             "CADDUpdater.buffer_variants record by record")
-        n = cnt["rows"]
-        if cnt["bad"]:
-            first = int(row_start[:n][(flags[:n] & N.CADDUPD_BAD) != 0][0])
-            line = int((text[:first] == 10).sum()) + 1
-            raise ValueError(f"line {line} of the export: the metaseq id does not have the four parts "
-                             f"chrom:pos:ref:alt ({cnt['bad']} such line(s))")
-        out_bytes = cnt["out_bytes"]
-        host_rows = rendered = None
-        if cnt["host_rows"]:
-            host_rows = torch.nonzero(flags[:n] & N.CADDUPD_ROW_HOST).flatten()
-            start = row_start[host_rows]
-            nxt = torch.where(host_rows + 1 < n, row_start[torch.clamp(host_rows + 1, max=max(n - 1, 0))],
-                              torch.full_like(start, nb))
-            span = nxt - start  # the row's line, and the skipped lines behind it
-            raw = text[self._spans(start, span)].cpu().numpy().tobytes()
-            recs, at = [], 0
-            for s in span.tolist():
-                f = raw[at:at + s].split(b"\n", 1)[0]
-                at += s
-                f = (f[:-1] if f.endswith(b"\r") and len(f) < s else f).split(b"\t")
-                recs.append({"record_primary_key": f[0].decode("utf-8", "surrogateescape"),
-                             "metaseq_id": f[1].decode("utf-8", "surrogateescape")})
-            u = CADDUpdater(tabs[0], tabs[1], self)
-            if chromosome is not None:
-                u.set_chromosome(chromosome)
-            u.buffer_variants(recs, skip_existing=False)
-            out = [("\t".join(t) + "\n").encode("utf-8", "surrogateescape") for t in u.update_buffer()]
-            kinds = []
-            for rec, t in zip(recs, u.update_buffer()):
-                _, _, r, a = rec["metaseq_id"].split(":")
-                kinds.append(N.CADD_NONE if t[2] == "{}" else N.CADD_INDEL if len(r) > 1 or len(a) > 1 else N.CADD_SNV)
-            for name in ("snv", "indel", "not_matched"):
-                cnt[name] += u.get_count(name)
-            new_len = torch.tensor([len(x) for x in out], dtype=torch.int64)
-            out_bytes += int(new_len.sum())
-            out_len[host_rows] = new_len.to(torch.int32).to(self.device)
-            kind[host_rows] = torch.tensor(kinds, dtype=torch.uint8).to(self.device)
-            rendered = (torch.from_numpy(np.frombuffer(b"".join(out), dtype=np.uint8).copy()).to(self.device),
-                        new_len.to(self.device))
-        cnt["out_bytes"] = out_bytes
-        out_text = self.empty(max(1, out_bytes), torch.uint8)
-        row_off = self.empty(n + 1, torch.int64)
-        totals = self.empty(2, torch.int64)
-        run("avdb_cadd_update_write" + suffix, tp, nb, n_lines, n, *shared, row_start, pk_len, kind, match, out_len,
-            flags, out_text, out_bytes, row_off, totals, *tail)
-        if rendered is not None:
-            out_text[self._spans(row_off[host_rows], rendered[1])] = rendered[0]
-        tot = totals.cpu().tolist()
-        if tot[1] or tot[0] != out_bytes:
-            raise N.NativeError("avdb_cadd_update_write" + suffix, N.AVDB_ERANGE,
-                                f"rows of {tot[0]} bytes do not fit the {out_bytes} the size pass gave")
-        return CaddUpdateRows(n, out_text[:out_bytes], row_off, kind[:n], flags[:n], cnt)
+        return slab_passes.cadd_update_rows(self, text, snv, indel, chromosome, skip_existing, contigs)
 
     # -- K14: the VCF files of an export ------------------------------------------
     def export_vcf(self, text, contigs=None, variants_per_file: int = 10_000_000) -> "ExportVcf":
@@ -1645,106 +1502,7 @@ class Engine:
         with the last one's metaseq id and the others are dropped; the VCF write pass
         then runs again.  Without such rows no row text comes to the host.  On a
         host-only engine the library's host entries run the same per-line code."""
-        vpf = int(variants_per_file)
-        if vpf < 1:
-            raise ValueError("variants_per_file must be at least 1")
-        text = self._as_text(text)
-        nb = text.numel()
-        n_lines = self._count_lines(text)
-        m = max(1, n_lines)
-        row_start, pk_hash, inv_start = (self.empty(m, torch.int64) for _ in range(3))
-        pk_len, ms_len, out_len, inv_pk_len, inv_out_len = (self.empty(m, torch.int32) for _ in range(5))
-        flags = self.empty(m, torch.uint8)
-        counts = self.empty(N.EXPVCF_N_COUNTS, torch.int64)
-        tp = text if nb else None
-        if self.host_only:
-            run, suffix, tail = self._call, "_host", ()
-        else:
-            ws = self.scratch("export_vcf", N.size("avdb_export_vcf_workspace_size", nb, n_lines))
-            run, suffix, tail = self._launch, "", (ws, ws.numel())
-        run("avdb_export_vcf_size" + suffix, tp, nb, n_lines, existing_contig_mask(contigs), row_start, pk_len, ms_len,
-            out_len, flags, pk_hash, inv_start, inv_pk_len, inv_out_len, counts, *tail)
-        cnt = dict(zip(N.EXPVCF_COUNTS, (int(x) for x in counts.cpu().numpy().astype(np.uint64))))
-        if cnt["lone_cr"]:
-            raise ValueError(f"{cnt['lone_cr']} carriage return(s) in the export that no newline follows: Python's "
-                             "text mode ends a line there and the device pass does not")
-        nv, ni = cnt["valid"], cnt["invalid"]
-        if cnt["bad"]:
-            first = int(row_start[:nv][(flags[:nv] & N.EXPVCF_BAD) != 0][0])
-            line = int((text[:first] == 10).sum()) + 1
-            raise ValueError(f"line {line} of the export: the metaseq id does not have the four parts "
-                             f"chrom:pos:ref:alt ({cnt['bad']} such line(s))")
-        n_files = nv // vpf + 1
-        # rows of one file whose keys hash alike: neighbours after one sort of the hash with the file folded in
-        # (equal (file, hash) pairs give equal sort keys; the host compare below sorts out any other)
-        order = same = None
-        n_cand = torch.zeros(1, dtype=torch.int64, device=self.device)
-        if nv > 1:
-            key = pk_hash[:nv]
-            if n_files > 1:
-                key = key + torch.div(torch.arange(nv, device=self.device), vpf, rounding_mode="floor") * _FILE_SALT
-            skey, order = torch.sort(key)
-            same = skey[1:] == skey[:-1]
-            n_cand = same.sum().view(1)
-        cnt["dropped"] = 0
-        file_rows = torch.arange(n_files, device=self.device) * vpf
-
-        def write(which, n, cols, nbytes):
-            out = self.empty(max(1, nbytes), torch.uint8)
-            row_off = self.empty(n + 1, torch.int64)
-            totals = self.empty(2, torch.int64)
-            run("avdb_export_vcf_write" + suffix, tp, nb, n_lines, which, n, *cols, out, nbytes, row_off, totals, *tail)
-            return out, row_off, totals
-
-        def check(name, tot, want):
-            if tot[1] or tot[0] != want:
-                raise N.NativeError("avdb_export_vcf_write" + suffix, N.AVDB_ERANGE,
-                                    f"{name} rows of {tot[0]} bytes do not fit the {want} the size pass gave")
-
-        vcf_cols = (row_start, pk_len, ms_len, out_len, flags)
-        vcf, vcf_off, vcf_tot = write(N.EXPVCF_STREAM_VCF, nv, vcf_cols, cnt["vcf_bytes"])
-        inv, inv_off, inv_tot = write(N.EXPVCF_STREAM_INVALID, ni, (inv_start, inv_pk_len, None, inv_out_len, None),
-                                      cnt["invalid_bytes"])
-        end = torch.cat([vcf_tot, inv_tot, n_cand, vcf_off[file_rows]]).cpu().tolist()
-        check("VCF", end[0:2], cnt["vcf_bytes"])
-        check("invalid", end[2:4], cnt["invalid_bytes"])
-        file_start = end[5:]
-        if end[4]:
-            member = torch.zeros(nv, dtype=torch.bool, device=self.device)
-            member[order[1:][same]] = True
-            member[order[:-1][same]] = True
-            rows = torch.nonzero(member).flatten()  # in file order
-            pl, ml = pk_len[rows].long(), ms_len[rows].long()
-            raw = text[self._spans(row_start[rows], pl + 1 + ml)].cpu().numpy().tobytes()
-            groups, at = {}, 0  # (file, key bytes) -> [(row, metaseq id)]
-            for r, p, q in zip(rows.tolist(), pl.tolist(), ml.tolist()):
-                groups.setdefault((r // vpf, raw[at:at + p]), []).append((r, raw[at + p + 1:at + p + 1 + q]))
-                at += p + 1 + q
-            first, rendered, dropped = [], [], []
-            for (_, pk), g in groups.items():
-                if len(g) > 1:  # variants[primaryKey] = metaseqId: the first one's place, the last one's id
-                    c, p, r, a = g[-1][1].split(b":")
-                    first.append(g[0][0])
-                    rendered.append(b"\t".join((c, p, pk, r, a, b".", b".", b".")) + b"\n")
-                    dropped += [x[0] for x in g[1:]]
-            if first:
-                first_t, dropped_t = (torch.tensor(x, dtype=torch.int64, device=self.device) for x in (first, dropped))
-                new_len = torch.tensor([len(x) for x in rendered], dtype=torch.int64)
-                cnt["vcf_bytes"] += int(new_len.sum()) - int(out_len[first_t].sum()) - int(out_len[dropped_t].sum())
-                cnt["dropped"] = len(dropped)
-                flags[first_t] |= N.EXPVCF_ROW_HOST
-                flags[dropped_t] |= N.EXPVCF_DROPPED
-                out_len[first_t] = new_len.to(torch.int32).to(self.device)
-                out_len[dropped_t] = 0
-                vcf, vcf_off, vcf_tot = write(N.EXPVCF_STREAM_VCF, nv, vcf_cols, cnt["vcf_bytes"])
-                blob = torch.from_numpy(np.frombuffer(b"".join(rendered), dtype=np.uint8).copy()).to(self.device)
-                vcf[self._spans(vcf_off[first_t], new_len.to(self.device))] = blob
-                end = torch.cat([vcf_tot, vcf_off[file_rows]]).cpu().tolist()
-                check("VCF", end[0:2], cnt["vcf_bytes"])
-                file_start = end[2:]
-        file_start = [int(x) for x in file_start] + [cnt["vcf_bytes"]]
-        return ExportVcf(vcf[:cnt["vcf_bytes"]], vcf_off, inv[:cnt["invalid_bytes"]], inv_off, flags[:nv], cnt, n_files,
-                         vpf, file_start)
+        return slab_passes.export_vcf(self, text, contigs, variants_per_file)
 
     # -- K15: a whole-genome VCF split by chromosome ------------------------------
     def split_chrom_map(self, mapping: Dict) -> "ChromMap":
@@ -1772,100 +1530,7 @@ class Engine:
         unplaced line comes before it; invalid UTF-8 elsewhere in a line is copied
         verbatim.  On a host-only engine the library's host entries run the same
         per-line code."""
-        if unknown not in ("raise", "keep"):
-            raise ValueError("unknown must be 'raise' or 'keep'")
-        if isinstance(chrom_map, dict):
-            chrom_map = self.split_chrom_map(chrom_map)
-        text = self._as_text(text)
-        nb = text.numel()
-        n_lines = self._count_lines(text)
-        m = max(1, n_lines)
-        code = self.empty(m, torch.uint8)
-        line_start = self.empty(m, torch.int64)
-        out_len = self.empty(m, torch.int32)
-        counts = self.empty(N.SPLIT_N_COUNTS, torch.int64)
-        tp = text if nb else None
-        handle = chrom_map.handle if chrom_map is not None else None
-        if self.host_only:
-            run, suffix, tail = self._call, "_host", ()
-        else:
-            ws = self.scratch("split_vcf", N.size("avdb_vcf_split_workspace_size", nb, n_lines))
-            run, suffix, tail = self._launch, "", (ws, ws.numel())
-        run("avdb_vcf_split_size" + suffix, tp, nb, n_lines, handle, code, line_start, out_len, counts, *tail)
-        cnt = [int(x) for x in counts.cpu().numpy().astype(np.uint64)]
-        n_of = cnt[N.SPLIT_COUNT_LINES:N.SPLIT_COUNT_LINES + N.SPLIT_N_STREAMS]
-        b_of = cnt[N.SPLIT_COUNT_BYTES:N.SPLIT_COUNT_BYTES + N.SPLIT_N_STREAMS]
-        comments, host_lines = cnt[N.SPLIT_COUNT_COMMENTS], cnt[N.SPLIT_COUNT_HOST_LINES]
-        first_other = cnt[N.SPLIT_COUNT_FIRST_OTHER] if n_of[N.SPLIT_OTHER] else None
-        mapping = chrom_map.mapping if chrom_map is not None else None
-
-        def stream_of_key(key: str) -> int:
-            label = key if mapping is None else mapping.get(key)
-            return CHROM_NAMES.index(label) if isinstance(label, str) and label in CHROM_NAMES else N.SPLIT_OTHER
-
-        decode_error = None  # (line, the UnicodeDecodeError) of the first line whose decode raises
-        if host_lines:
-            rows = torch.nonzero(out_len[:n_lines] < 0).flatten()  # bit 31: N.SPLIT_LINE_HOST
-            begin = line_start[rows]
-            end = torch.where(rows + 1 < n_lines, line_start[torch.clamp(rows + 1, max=n_lines - 1)],
-                              torch.full_like(begin, nb))
-            raw = text[self._spans(begin, end - begin)].cpu().numpy().tobytes()
-            old_code, old_len = code[rows].cpu().tolist(), (out_len[rows] & 0x7FFFFFFF).cpu().tolist()
-            new_code, new_len, at = [], [], 0
-            for i, (r, span) in enumerate(zip(rows.tolist(), (end - begin).tolist())):
-                line = raw[at:at + span]
-                at += span
-                try:
-                    line = line.decode("utf-8").rstrip()
-                except UnicodeDecodeError as e:
-                    if decode_error is None:
-                        decode_error = (r, e)
-                    new_code.append(old_code[i])
-                    new_len.append(old_len[i])
-                    continue
-                if line.startswith("#"):
-                    c, ln = N.SPLIT_NONE, 0
-                else:
-                    c, ln = stream_of_key(line.split("\t")[0]), len(line.encode("utf-8")) + 1
-                new_code.append(c)
-                new_len.append(ln)
-                if old_code[i] < N.SPLIT_N_STREAMS:
-                    n_of[old_code[i]] -= 1
-                    b_of[old_code[i]] -= old_len[i]
-                else:
-                    comments -= 1
-                if c < N.SPLIT_N_STREAMS:
-                    n_of[c] += 1
-                    b_of[c] += ln
-                else:
-                    comments += 1
-            code[rows] = torch.tensor(new_code, dtype=torch.uint8).to(self.device)
-            out_len[rows] = torch.tensor(new_len, dtype=torch.int32).to(self.device)
-            others = torch.nonzero(code[:n_lines] == N.SPLIT_OTHER).flatten()
-            first_other = int(others[0]) if others.numel() else None
-        if decode_error is not None and (unknown == "keep" or first_other is None or decode_error[0] < first_other):
-            raise decode_error[1]
-        if first_other is not None and unknown == "raise":
-            b = int(line_start[first_other])
-            line = text[b:b + int(out_len[first_other] & 0x7FFFFFFF) - 1].cpu().numpy().tobytes()
-            key = line.decode("utf-8", "replace").split("\t")[0]
-            err = KeyError(key if mapping is None or key not in mapping else mapping[key])
-            err.line = first_other + 1
-            if hasattr(err, "add_note"):
-                err.add_note(f"line {err.line} of the slab: no chr<label>.vcf takes it")
-            raise err
-        total = sum(b_of)
-        out = self.empty(max(1, total), torch.uint8)
-        stream_off = self.empty(N.SPLIT_N_STREAMS + 1, torch.int64)
-        totals = self.empty(2, torch.int64)
-        run("avdb_vcf_split_write" + suffix, tp, nb, n_lines, code, line_start, out_len, out, total, stream_off, None,
-            totals, *tail)
-        end = torch.cat([totals, stream_off]).cpu().tolist()
-        if end[1] or end[0] != total:
-            raise N.NativeError("avdb_vcf_split_write" + suffix, N.AVDB_ERANGE,
-                                f"lines of {end[0]} bytes do not fit the {total} the size pass gave")
-        cnt = {"lines": n_of, "bytes": b_of, "comments": comments, "host_lines": host_lines}
-        return SplitVcf(out[:total], [int(x) for x in end[2:]], cnt, first_other)
+        return slab_passes.split_vcf(self, text, chrom_map, unknown)
 
     # -- K10: CADD table and allele join ---------------------------------------
     def new_cadd_counters(self) -> torch.Tensor:
@@ -1877,24 +1542,7 @@ class Engine:
         tensor) -> the table's columns on this engine's device.  One sync (the line
         count) before the build, one after (the counts).  On a host-only engine the
         library's host entry runs the same per-line code."""
-        text = self._as_text(text)
-        nb = text.numel()
-        n_lines = self._count_lines(text)
-        m = max(1, n_lines)
-        cols = [self.empty(m, dt) for dt in (torch.uint8, torch.int32, torch.int64, torch.int32, torch.int64,
-                                             torch.int32, torch.float64, torch.float64, torch.uint8)]
-        first_row = self.empty(N.CADD_N_CONTIGS, torch.int32)
-        end_row = self.empty(N.CADD_N_CONTIGS, torch.int32)
-        counts = self.empty(N.CADD_N_COUNTS, torch.int64)
-        args = (text if nb else None, nb, n_lines, *cols, first_row, end_row, counts)
-        if self.host_only:
-            self._call("avdb_cadd_table_build_host", *args)
-        else:
-            ws = self.scratch("cadd_build", N.size("avdb_cadd_workspace_size", nb, n_lines))
-            self._launch("avdb_cadd_table_build", *args, ws, ws.numel())
-        cnt = counts.cpu().numpy().astype(np.uint64)
-        n_rows = int(cnt[N.CADD_COUNT_ROWS])
-        return CaddColumns(text, n_rows, *[c[:n_rows] for c in cols], first_row, end_row, cnt)
+        return slab_passes.cadd_table_build(self, text)
 
     def cadd_match(self, snv: Optional["CaddColumns"], indel: Optional["CaddColumns"], b: RecordBatch,
                    counters: Optional[torch.Tensor] = None, out=None):

@@ -1,0 +1,377 @@
+"""The passes over a '\\n'-separated text slab behind :class:`~annotatedvdb_amd.engine.Engine`:
+K10a ``cadd_table_build``, K12 ``existing_table_build``, K13 ``cadd_update_rows``, K14
+``export_vcf`` and K15 ``split_vcf``.
+
+The two-pass ones have one shape: line count -> size pass -> its counts to the host (second
+sync) -> the rows the device leaves to the host rendered here -> outputs allocated -> write
+pass -> the host-rendered rows copied into their spans -> totals checked (third sync).
+:class:`SlabPass` holds what that shape needs from every pass; the functions below hold what
+differs.  The ``Engine`` methods of the same names carry the contracts and delegate here.
+"""
+
+from __future__ import annotations
+
+import ctypes
+from typing import List
+
+import numpy as np
+import torch
+
+from . import _native as N
+from . import engine as E
+from .chromosomes import CHROM_NAMES
+
+_FILE_SALT = -7046029254386353131  # 0x9E3779B97F4A7C15 as int64: folds a row's file number into its key hash (K14)
+
+
+class SlabPass:
+    """One slab on the engine's device, its line count (a sync), and the library's entries
+    for it: the ``_host`` ones on a host-only engine, else the device ones with the
+    engine's scratch workspace ``scratch_name``, sized by ``workspace_size_entry``."""
+
+    def __init__(self, engine, text, scratch_name: str, workspace_size_entry: str):
+        self.engine = engine
+        self.text = engine._as_text(text)
+        self.nb = self.text.numel()
+        self.n_lines = engine._count_lines(self.text)
+        self.m = max(1, self.n_lines)  # entries of a per-line array: none is empty
+        self.tp = self.text if self.nb else None
+        if engine.host_only:
+            self._run, self.suffix, self._tail = engine._call, "_host", ()
+        else:
+            ws = engine.scratch(scratch_name, N.size(workspace_size_entry, self.nb, self.n_lines))
+            self._run, self.suffix, self._tail = engine._launch, "", (ws, ws.numel())
+
+    def cols(self, *dtypes) -> List[torch.Tensor]:
+        """Per-line (or per-row) arrays for the entries to fill."""
+        return [self.engine.empty(self.m, dt) for dt in dtypes]
+
+    def call(self, entry: str, *args):
+        return self._run(entry + self.suffix, *args, *self._tail)
+
+    def counts(self, tensor: torch.Tensor, names=None):
+        """A pass's counts on the host (a sync): a dict by ``names``, or a list."""
+        vals = [int(x) for x in tensor.cpu().numpy().astype(np.uint64)]
+        return vals if names is None else dict(zip(names, vals))
+
+    def rows_bytes(self, start: torch.Tensor, length: torch.Tensor) -> List[bytes]:
+        """The text's spans ``[start[i], start[i] + length[i])``: one gather, one copy to the host."""
+        raw = self.text[self.engine._spans(start, length)].cpu().numpy().tobytes()
+        out, at = [], 0
+        for n in length.tolist():
+            out.append(raw[at:at + n])
+            at += n
+        return out
+
+    def lengths(self, rendered: List[bytes]) -> torch.Tensor:
+        return torch.tensor([len(x) for x in rendered], dtype=torch.int64).to(self.engine.device)
+
+    def splice(self, out: torch.Tensor, off_at_rows: torch.Tensor, rendered: List[bytes]) -> torch.Tensor:
+        """Host-rendered rows into their spans of ``out``, which start at ``off_at_rows``; their lengths."""
+        new_len = self.lengths(rendered)
+        blob = torch.from_numpy(np.frombuffer(b"".join(rendered), dtype=np.uint8).copy()).to(self.engine.device)
+        out[self.engine._spans(off_at_rows, new_len)] = blob
+        return new_len
+
+    def check_totals(self, entry: str, got, want, what: str):
+        """``got``: a write pass's totals, the last one its count of capacities exceeded;
+        ``want``: the bytes the outputs were allocated with (an int for one stream)."""
+        if isinstance(want, int):
+            want, text = [want], f"{what} of {got[0]} bytes do not fit the {want} the size pass gave"
+        else:
+            text = f"{what} {got[:-1]} do not fit the sizes the size pass gave"
+        if got[-1] or got[:-1] != want:
+            raise N.NativeError(entry + self.suffix, N.AVDB_ERANGE, text)
+
+    @staticmethod
+    def raise_lone_cr(n: int, advice: str):
+        raise ValueError(f"{n} carriage return(s) in the export that no newline follows: Python's "
+                         f"text mode ends a line there and the device {advice}")
+
+    def raise_bad_metaseq(self, row_start, flags, bit: int, n_rows: int, count: int):
+        first = int(row_start[:n_rows][(flags[:n_rows] & bit) != 0][0])
+        line = int((self.text[:first] == 10).sum()) + 1
+        raise ValueError(f"line {line} of the export: the metaseq id does not have the four parts "
+                         f"chrom:pos:ref:alt ({count} such line(s))")
+
+
+def _lines_to_next(sp: SlabPass, rows, start, n: int) -> torch.Tensor:
+    """Bytes from the starts of ``rows`` (indices into ``start[:n]``) to the next entry's start, or the text's end."""
+    nxt = torch.where(rows + 1 < n, start[torch.clamp(rows + 1, max=max(n - 1, 0))],
+                      torch.full_like(start[rows], sp.nb))
+    return nxt - start[rows]
+
+
+def cadd_table_build(engine, text):
+    sp = SlabPass(engine, text, "cadd_build", "avdb_cadd_workspace_size")
+    cols = sp.cols(torch.uint8, torch.int32, torch.int64, torch.int32, torch.int64, torch.int32, torch.float64,
+                   torch.float64, torch.uint8)
+    first_row = engine.empty(N.CADD_N_CONTIGS, torch.int32)
+    end_row = engine.empty(N.CADD_N_CONTIGS, torch.int32)
+    counts = engine.empty(N.CADD_N_COUNTS, torch.int64)
+    sp.call("avdb_cadd_table_build", sp.tp, sp.nb, sp.n_lines, *cols, first_row, end_row, counts)
+    cnt = counts.cpu().numpy().astype(np.uint64)
+    n_rows = int(cnt[N.CADD_COUNT_ROWS])
+    return E.CaddColumns(sp.text, n_rows, *[c[:n_rows] for c in cols], first_row, end_row, cnt)
+
+
+def existing_table_build(engine, text, contigs=None):
+    sp = SlabPass(engine, text, "existing_build", "avdb_existing_workspace_size")
+    key_len, pk_len, frag_len, flags, row_off = sp.cols(torch.int32, torch.int32, torch.int32, torch.uint8, torch.int64)
+    counts = engine.empty(N.EXIST_N_COUNTS, torch.int64)
+    sp.call("avdb_existing_size", sp.tp, sp.nb, sp.n_lines, E.existing_contig_mask(contigs), key_len, pk_len, frag_len,
+            flags, row_off, counts)
+    cnt = sp.counts(counts, N.EXIST_COUNTS)
+    if cnt["lone_cr"]:
+        sp.raise_lone_cr(cnt["lone_cr"], "build does not; load this export with ExistingVariants.from_tsv "
+                                         "(--existingHost)")
+    n = cnt["rows"]
+    frag_bytes = cnt["frag_bytes"]
+    host_rows = rendered = None
+    if cnt["frag_host"]:
+        # the rows repr() escapes in: their pk and bin bytes ("pk<TAB>bin") to the host
+        host_rows = torch.nonzero(flags[:n] & N.EXIST_FRAG_HOST).flatten()
+        kl, pl = key_len[host_rows].long(), pk_len[host_rows].long()
+        fl = frag_len[host_rows].long()
+        span = fl - 36 + 1  # len(pk) + 1 + len(bin): the fixed text of a fragment is 36 bytes
+        rendered = [repr({"primary_key": b[:p].decode("utf-8"), "bin_index": b[p + 1:].decode("utf-8")}).encode("utf-8")
+                    for p, b in zip(pl.tolist(), sp.rows_bytes(row_off[host_rows] + kl + 1, span))]
+        frag_bytes += sum(map(len, rendered)) - int(fl.sum())
+        frag_len[host_rows] = sp.lengths(rendered).to(torch.int32)
+    keys = engine.empty(max(1, cnt["key_bytes"]), torch.uint8)
+    pks = engine.empty(max(1, cnt["pk_bytes"]), torch.uint8)
+    frag = engine.empty(max(1, frag_bytes), torch.uint8)
+    key_off, pk_off, frag_off = (engine.empty(n + 1, torch.int64) for _ in range(3))
+    totals = engine.empty(4, torch.int64)
+    sp.call("avdb_existing_write", sp.tp, sp.nb, sp.n_lines, n, key_len, pk_len, frag_len, flags, row_off, keys,
+            cnt["key_bytes"], key_off, pks, cnt["pk_bytes"], pk_off, frag, frag_bytes, frag_off, totals)
+    if rendered is not None:
+        sp.splice(frag, frag_off[host_rows], rendered)
+    sp.check_totals("avdb_existing_write", totals.cpu().tolist(), [cnt["key_bytes"], cnt["pk_bytes"], frag_bytes],
+                    "blob totals")
+    return E.ExistingColumns(n, keys, key_off, pks, pk_off, frag, frag_off, flags[:n], cnt)
+
+
+def cadd_update_rows(engine, text, snv, indel, chromosome=None, skip_existing: bool = True, contigs=None):
+    from .cadd import CADDUpdater, CaddTable  # (cadd imports the engine)
+    tabs = [t if t is None or isinstance(t, CaddTable) else CaddTable(t, engine) for t in (snv, indel)]
+    for t in tabs:
+        if t is not None and t.cols.text.device != engine.device:
+            raise ValueError("CADD table lives on another device than this engine")
+    views = [t.cols.view() if t is not None else None for t in tabs]
+    vp = [ctypes.byref(v) if v is not None else None for v in views]
+    chrom = None
+    if chromosome is not None:
+        label = str(chromosome).replace("chr", "")  # set_chromosome, then buffer_update_values' prefix
+        chrom = (label if "chr" in label else "chr" + label).encode("utf-8")
+        if not 0 < len(chrom) <= N.CADDUPD_CHROM_MAX:
+            raise ValueError(f"chromosome text of {len(chrom)} bytes (1 .. {N.CADDUPD_CHROM_MAX} taken)")
+    shared = (*vp, chrom, len(chrom) if chrom else 0)
+    sp = SlabPass(engine, text, "cadd_update", "avdb_cadd_update_workspace_size")
+    row_start, pk_len, out_len, match, kind, flags = sp.cols(torch.int64, torch.int32, torch.int32, torch.int32,
+                                                             torch.uint8, torch.uint8)
+    counts = engine.empty(N.CADDUPD_N_COUNTS, torch.int64)
+    sp.call("avdb_cadd_update_size", sp.tp, sp.nb, sp.n_lines, *shared, E.existing_contig_mask(contigs),
+            N.CADDUPD_SKIP_EXISTING if skip_existing else 0, row_start, pk_len, kind, match, out_len, flags, counts)
+    cnt = sp.counts(counts, N.CADDUPD_COUNTS)
+    if cnt["lone_cr"]:
+        sp.raise_lone_cr(cnt["lone_cr"], "pass does not; feed this export to CADDUpdater.buffer_variants record by "
+                                         "record")
+    n = cnt["rows"]
+    if cnt["bad"]:
+        sp.raise_bad_metaseq(row_start, flags, N.CADDUPD_BAD, n, cnt["bad"])
+    out_bytes = cnt["out_bytes"]
+    host_rows = rendered = None
+    if cnt["host_rows"]:
+        host_rows = torch.nonzero(flags[:n] & N.CADDUPD_ROW_HOST).flatten()
+        recs = []
+        # a row's span: its line, and the skipped lines behind it
+        for b in sp.rows_bytes(row_start[host_rows], _lines_to_next(sp, host_rows, row_start, n)):
+            f = b.split(b"\n", 1)[0]
+            f = (f[:-1] if f.endswith(b"\r") and len(f) < len(b) else f).split(b"\t")
+            recs.append({"record_primary_key": f[0].decode("utf-8", "surrogateescape"),
+                         "metaseq_id": f[1].decode("utf-8", "surrogateescape")})
+        u = CADDUpdater(tabs[0], tabs[1], engine)
+        if chromosome is not None:
+            u.set_chromosome(chromosome)
+        u.buffer_variants(recs, skip_existing=False)
+        rendered = [("\t".join(t) + "\n").encode("utf-8", "surrogateescape") for t in u.update_buffer()]
+        kinds = []
+        for rec, t in zip(recs, u.update_buffer()):
+            _, _, r, a = rec["metaseq_id"].split(":")
+            kinds.append(N.CADD_NONE if t[2] == "{}" else N.CADD_INDEL if len(r) > 1 or len(a) > 1 else N.CADD_SNV)
+        for name in ("snv", "indel", "not_matched"):
+            cnt[name] += u.get_count(name)
+        out_bytes += sum(map(len, rendered))
+        out_len[host_rows] = sp.lengths(rendered).to(torch.int32)
+        kind[host_rows] = torch.tensor(kinds, dtype=torch.uint8).to(engine.device)
+    cnt["out_bytes"] = out_bytes
+    out_text = engine.empty(max(1, out_bytes), torch.uint8)
+    row_off = engine.empty(n + 1, torch.int64)
+    totals = engine.empty(2, torch.int64)
+    sp.call("avdb_cadd_update_write", sp.tp, sp.nb, sp.n_lines, n, *shared, row_start, pk_len, kind, match, out_len,
+            flags, out_text, out_bytes, row_off, totals)
+    if rendered is not None:
+        sp.splice(out_text, row_off[host_rows], rendered)
+    sp.check_totals("avdb_cadd_update_write", totals.cpu().tolist(), out_bytes, "rows")
+    return E.CaddUpdateRows(n, out_text[:out_bytes], row_off, kind[:n], flags[:n], cnt)
+
+
+def export_vcf(engine, text, contigs=None, variants_per_file: int = 10_000_000):
+    vpf = int(variants_per_file)
+    if vpf < 1:
+        raise ValueError("variants_per_file must be at least 1")
+    sp = SlabPass(engine, text, "export_vcf", "avdb_export_vcf_workspace_size")
+    row_start, pk_hash, inv_start = sp.cols(*[torch.int64] * 3)
+    pk_len, ms_len, out_len, inv_pk_len, inv_out_len, flags = sp.cols(*[torch.int32] * 5, torch.uint8)
+    counts = engine.empty(N.EXPVCF_N_COUNTS, torch.int64)
+    sp.call("avdb_export_vcf_size", sp.tp, sp.nb, sp.n_lines, E.existing_contig_mask(contigs), row_start, pk_len,
+            ms_len, out_len, flags, pk_hash, inv_start, inv_pk_len, inv_out_len, counts)
+    cnt = sp.counts(counts, N.EXPVCF_COUNTS)
+    if cnt["lone_cr"]:
+        sp.raise_lone_cr(cnt["lone_cr"], "pass does not")
+    nv, ni = cnt["valid"], cnt["invalid"]
+    if cnt["bad"]:
+        sp.raise_bad_metaseq(row_start, flags, N.EXPVCF_BAD, nv, cnt["bad"])
+    n_files = nv // vpf + 1
+    # rows of one file whose keys hash alike: neighbours after one sort of the hash with the file folded in
+    # (equal (file, hash) pairs give equal sort keys; the host compare below sorts out any other)
+    order = same = None
+    n_cand = torch.zeros(1, dtype=torch.int64, device=engine.device)
+    if nv > 1:
+        key = pk_hash[:nv]
+        if n_files > 1:
+            key = key + torch.div(torch.arange(nv, device=engine.device), vpf, rounding_mode="floor") * _FILE_SALT
+        skey, order = torch.sort(key)
+        same = skey[1:] == skey[:-1]
+        n_cand = same.sum().view(1)
+    cnt["dropped"] = 0
+    file_rows = torch.arange(n_files, device=engine.device) * vpf
+
+    def write(which, n, cols, nbytes):
+        out = engine.empty(max(1, nbytes), torch.uint8)
+        row_off = engine.empty(n + 1, torch.int64)
+        totals = engine.empty(2, torch.int64)
+        sp.call("avdb_export_vcf_write", sp.tp, sp.nb, sp.n_lines, which, n, *cols, out, nbytes, row_off, totals)
+        return out, row_off, totals
+
+    vcf_cols = (row_start, pk_len, ms_len, out_len, flags)
+    vcf, vcf_off, vcf_tot = write(N.EXPVCF_STREAM_VCF, nv, vcf_cols, cnt["vcf_bytes"])
+    inv, inv_off, inv_tot = write(N.EXPVCF_STREAM_INVALID, ni, (inv_start, inv_pk_len, None, inv_out_len, None),
+                                  cnt["invalid_bytes"])
+    end = torch.cat([vcf_tot, inv_tot, n_cand, vcf_off[file_rows]]).cpu().tolist()
+    sp.check_totals("avdb_export_vcf_write", end[0:2], cnt["vcf_bytes"], "VCF rows")
+    sp.check_totals("avdb_export_vcf_write", end[2:4], cnt["invalid_bytes"], "invalid rows")
+    file_start = end[5:]
+    if end[4]:
+        member = torch.zeros(nv, dtype=torch.bool, device=engine.device)
+        member[order[1:][same]] = True
+        member[order[:-1][same]] = True
+        rows = torch.nonzero(member).flatten()  # in file order
+        pl = pk_len[rows].long()
+        groups = {}  # (file, key bytes) -> [(row, metaseq id)]
+        for r, p, b in zip(rows.tolist(), pl.tolist(), sp.rows_bytes(row_start[rows], pl + 1 + ms_len[rows].long())):
+            groups.setdefault((r // vpf, b[:p]), []).append((r, b[p + 1:]))
+        first, rendered, dropped = [], [], []
+        for (_, pk), g in groups.items():
+            if len(g) > 1:  # variants[primaryKey] = metaseqId: the first one's place, the last one's id
+                c, p, r, a = g[-1][1].split(b":")
+                first.append(g[0][0])
+                rendered.append(b"\t".join((c, p, pk, r, a, b".", b".", b".")) + b"\n")
+                dropped += [x[0] for x in g[1:]]
+        if first:
+            first_t, dropped_t = (torch.tensor(x, dtype=torch.int64, device=engine.device) for x in (first, dropped))
+            cnt["vcf_bytes"] += sum(map(len, rendered)) - int(out_len[first_t].sum()) - int(out_len[dropped_t].sum())
+            cnt["dropped"] = len(dropped)
+            flags[first_t] |= N.EXPVCF_ROW_HOST
+            flags[dropped_t] |= N.EXPVCF_DROPPED
+            out_len[first_t] = sp.lengths(rendered).to(torch.int32)
+            out_len[dropped_t] = 0
+            vcf, vcf_off, vcf_tot = write(N.EXPVCF_STREAM_VCF, nv, vcf_cols, cnt["vcf_bytes"])
+            sp.splice(vcf, vcf_off[first_t], rendered)
+            end = torch.cat([vcf_tot, vcf_off[file_rows]]).cpu().tolist()
+            sp.check_totals("avdb_export_vcf_write", end[0:2], cnt["vcf_bytes"], "VCF rows")
+            file_start = end[2:]
+    file_start = [int(x) for x in file_start] + [cnt["vcf_bytes"]]
+    return E.ExportVcf(vcf[:cnt["vcf_bytes"]], vcf_off, inv[:cnt["invalid_bytes"]], inv_off, flags[:nv], cnt, n_files,
+                       vpf, file_start)
+
+
+def split_vcf(engine, text, chrom_map=None, unknown: str = "raise"):
+    if unknown not in ("raise", "keep"):
+        raise ValueError("unknown must be 'raise' or 'keep'")
+    if isinstance(chrom_map, dict):
+        chrom_map = engine.split_chrom_map(chrom_map)
+    sp = SlabPass(engine, text, "split_vcf", "avdb_vcf_split_workspace_size")
+    n_lines = sp.n_lines
+    code, line_start, out_len = sp.cols(torch.uint8, torch.int64, torch.int32)
+    counts = engine.empty(N.SPLIT_N_COUNTS, torch.int64)
+    handle = chrom_map.handle if chrom_map is not None else None
+    sp.call("avdb_vcf_split_size", sp.tp, sp.nb, n_lines, handle, code, line_start, out_len, counts)
+    cnt = sp.counts(counts)
+    n_of = cnt[N.SPLIT_COUNT_LINES:N.SPLIT_COUNT_LINES + N.SPLIT_N_STREAMS]
+    b_of = cnt[N.SPLIT_COUNT_BYTES:N.SPLIT_COUNT_BYTES + N.SPLIT_N_STREAMS]
+    comments, host_lines = cnt[N.SPLIT_COUNT_COMMENTS], cnt[N.SPLIT_COUNT_HOST_LINES]
+    first_other = cnt[N.SPLIT_COUNT_FIRST_OTHER] if n_of[N.SPLIT_OTHER] else None
+    mapping = chrom_map.mapping if chrom_map is not None else None
+
+    def stream_of_key(key: str) -> int:
+        label = key if mapping is None else mapping.get(key)
+        return CHROM_NAMES.index(label) if isinstance(label, str) and label in CHROM_NAMES else N.SPLIT_OTHER
+
+    decode_error = None  # (line, the UnicodeDecodeError) of the first line whose decode raises
+    if host_lines:
+        rows = torch.nonzero(out_len[:n_lines] < 0).flatten()  # bit 31: N.SPLIT_LINE_HOST
+        old_code, old_len = code[rows].cpu().tolist(), (out_len[rows] & 0x7FFFFFFF).cpu().tolist()
+        new_code, new_len = [], []
+        for i, (r, line) in enumerate(zip(rows.tolist(), sp.rows_bytes(line_start[rows],
+                                                                       _lines_to_next(sp, rows, line_start, n_lines)))):
+            try:
+                line = line.decode("utf-8").rstrip()
+            except UnicodeDecodeError as e:
+                if decode_error is None:
+                    decode_error = (r, e)
+                new_code.append(old_code[i])
+                new_len.append(old_len[i])
+                continue
+            if line.startswith("#"):
+                c, ln = N.SPLIT_NONE, 0
+            else:
+                c, ln = stream_of_key(line.split("\t")[0]), len(line.encode("utf-8")) + 1
+            new_code.append(c)
+            new_len.append(ln)
+            if old_code[i] < N.SPLIT_N_STREAMS:
+                n_of[old_code[i]] -= 1
+                b_of[old_code[i]] -= old_len[i]
+            else:
+                comments -= 1
+            if c < N.SPLIT_N_STREAMS:
+                n_of[c] += 1
+                b_of[c] += ln
+            else:
+                comments += 1
+        code[rows] = torch.tensor(new_code, dtype=torch.uint8).to(engine.device)
+        out_len[rows] = torch.tensor(new_len, dtype=torch.int32).to(engine.device)
+        others = torch.nonzero(code[:n_lines] == N.SPLIT_OTHER).flatten()
+        first_other = int(others[0]) if others.numel() else None
+    if decode_error is not None and (unknown == "keep" or first_other is None or decode_error[0] < first_other):
+        raise decode_error[1]
+    if first_other is not None and unknown == "raise":
+        b = int(line_start[first_other])
+        line = sp.text[b:b + int(out_len[first_other] & 0x7FFFFFFF) - 1].cpu().numpy().tobytes()
+        key = line.decode("utf-8", "replace").split("\t")[0]
+        err = KeyError(key if mapping is None or key not in mapping else mapping[key])
+        err.line = first_other + 1
+        if hasattr(err, "add_note"):
+            err.add_note(f"line {err.line} of the slab: no chr<label>.vcf takes it")
+        raise err
+    total = sum(b_of)
+    out = engine.empty(max(1, total), torch.uint8)
+    stream_off = engine.empty(N.SPLIT_N_STREAMS + 1, torch.int64)
+    totals = engine.empty(2, torch.int64)
+    sp.call("avdb_vcf_split_write", sp.tp, sp.nb, n_lines, code, line_start, out_len, out, total, stream_off, None,
+            totals)
+    end = torch.cat([totals, stream_off]).cpu().tolist()
+    sp.check_totals("avdb_vcf_split_write", end[0:2], total, "lines")
+    cnt = {"lines": n_of, "bytes": b_of, "comments": comments, "host_lines": host_lines}
+    return E.SplitVcf(out[:total], [int(x) for x in end[2:]], cnt, first_other)

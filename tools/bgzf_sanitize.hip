@@ -15,25 +15,20 @@
 // fine, any sanitizer report is not.  Exit status 0 and a last line "clean" when done.
 #include "../annotatedvdb_amd/csrc/avdb_inflate.hpp"
 
-#include <stdio.h>
-#include <stdlib.h>
+#include "sanitize_common.hpp"
+
 #include <string.h>
 
-#include <memory>
-#include <vector>
-
 using namespace avdb;
-
-void avdb_set_error(const char*, ...) {}
 
 static const uint8_t kSentinel = 0xA5;
 
 // decode `bytes` of a member (a heap copy of exactly that size) that states `isize`;
 // the status, or -1 if a byte outside an OK member's output changed
 static int decode(inflate::State& S, inflate::Window& W, const uint8_t* member, size_t bytes, uint32_t isize, bool* ok) {
-  std::unique_ptr<uint8_t[]> in(new uint8_t[bytes ? bytes : 1]);
+  auto in = exact<uint8_t>(bytes);
   memcpy(in.get(), member, bytes);
-  std::unique_ptr<uint8_t[]> out(new uint8_t[isize ? isize : 1]);
+  auto out = exact<uint8_t>(isize);
   memset(out.get(), kSentinel, isize ? isize : 1);
   const uint32_t st = inflate::inflate_member(inflate::Lanes{0, 1}, S, W.b, in.get(), bytes, 0, 0, isize, out.get(), isize);
   *ok = st == AVDB_BGZF_OK;
@@ -48,15 +43,7 @@ int main(int argc, char** argv) {
     fprintf(stderr, "usage: %s corpus.bgzf [mutations]\n", argv[0]);
     return 2;
   }
-  FILE* fh = fopen(argv[1], "rb");
-  if (!fh) {
-    perror(argv[1]);
-    return 2;
-  }
-  std::vector<uint8_t> data;
-  uint8_t buf[65536];
-  for (size_t k; (k = fread(buf, 1, sizeof buf, fh)) > 0;) data.insert(data.end(), buf, buf + k);
-  fclose(fh);
+  const std::vector<uint8_t> data = read_file(argv[1]);
   const long mutations = argc > 2 ? atol(argv[2]) : 2000;
 
   struct Span {
@@ -88,31 +75,24 @@ int main(int argc, char** argv) {
   }
   printf("%zu of %zu members OK\n", n_ok, members.size());
 
-  uint64_t rng = 0x9E3779B97F4A7C15ull;  // xorshift64, fixed seed
-  auto next = [&rng]() {
-    rng ^= rng << 13;
-    rng ^= rng >> 7;
-    rng ^= rng << 17;
-    return rng;
-  };
   std::vector<uint8_t> work;
   for (long it = 0; it < mutations; ++it) {
     // every other time the member that holds a random byte of the corpus (the long streams), else any member
-    size_t pick = next() % members.size();
+    size_t pick = rnd() % members.size();
     if (it & 1) {
-      const size_t byte = next() % data.size();
+      const size_t byte = rnd() % data.size();
       for (pick = 0; pick + 1 < members.size() && members[pick + 1].at <= byte;) ++pick;
     }
     const Span& s = members[pick];
     work.assign(data.begin() + s.at, data.begin() + s.at + s.m.total_bytes);
     size_t bytes = work.size();
-    const uint64_t kind = next() % 8;
+    const uint64_t kind = rnd() % 8;
     if (kind == 0) {
-      bytes = next() % (work.size() + 1);  // truncated: the caller's buffer ends inside the member
+      bytes = rnd() % (work.size() + 1);  // truncated: the caller's buffer ends inside the member
     } else if (kind == 1 && s.m.total_bytes > s.m.hdr_bytes + 9) {
       // a shorter stream with BSIZE and the trailer moved to match (the first subfield is BC in the corpus' members
       // but one; there the flip below is what happens)
-      const size_t cut = 1 + next() % (s.m.total_bytes - s.m.hdr_bytes - 9);
+      const size_t cut = 1 + rnd() % (s.m.total_bytes - s.m.hdr_bytes - 9);
       if (work[12] == 'B' && work[13] == 'C') {
         memmove(work.data() + work.size() - 8 - cut, work.data() + work.size() - 8, 8);
         bytes = work.size() - cut;
@@ -121,7 +101,7 @@ int main(int argc, char** argv) {
       }
     } else {
       const int flips = kind == 2 ? 3 : 1;
-      for (int f = 0; f < flips; ++f) work[next() % work.size()] ^= uint8_t(1u << (next() % 8));
+      for (int f = 0; f < flips; ++f) work[rnd() % work.size()] ^= uint8_t(1u << (rnd() % 8));
     }
     bool ok;
     const int st = decode(*S, *W, work.data(), bytes, s.m.isize, &ok);

@@ -17,26 +17,7 @@
 // "clean" when done.
 #include "../annotatedvdb_amd/csrc/avdb_existing.hip"
 
-#include <stdio.h>
-#include <stdlib.h>
-
-#include <memory>
-
-void avdb_set_error(const char*, ...) {}
-namespace avdb {
-int text_line_starts(const uint8_t*, size_t, size_t, void*, uint64_t*, hipStream_t) { return AVDB_EHIP; }
-}  // namespace avdb
-
-static uint64_t g_seed = 0x9E3779B97F4A7C15ull;
-static uint64_t rnd() {
-  g_seed ^= g_seed << 13;
-  g_seed ^= g_seed >> 7;
-  g_seed ^= g_seed << 17;
-  return g_seed;
-}
-
-template <class T>
-static std::unique_ptr<T[]> exact(size_t n) { return std::unique_ptr<T[]>(new T[n ? n : 1]); }
+#include "sanitize_common.hpp"
 
 // both passes over text[0, bytes) with n_lines as given; hostile: overwrite some
 // lengths / offsets between the passes.  Returns the write pass's return code.
@@ -75,23 +56,12 @@ static int run(const avdb_ctx* ctx, const uint8_t* src, size_t bytes, size_t n_l
                                   reinterpret_cast<uint8_t*>(frag.get()), tot[2], fo.get(), totals);
 }
 
-static size_t count_lines(const uint8_t* t, size_t n) {
-  size_t k = 0;
-  for (size_t i = 0; i < n; ++i) k += t[i] == '\n';
-  return k + (n && t[n - 1] != '\n');
-}
-
 int main(int argc, char** argv) {
   if (argc < 2) {
     fprintf(stderr, "usage: %s export.tsv [mutations]\n", argv[0]);
     return 2;
   }
-  FILE* f = fopen(argv[1], "rb");
-  if (!f) return 2;
-  std::vector<uint8_t> text;
-  uint8_t buf[65536];
-  for (size_t n; (n = fread(buf, 1, sizeof buf, f)) > 0;) text.insert(text.end(), buf, buf + n);
-  fclose(f);
+  const std::vector<uint8_t> text = read_file(argv[1]);
   const long mutations = argc > 2 ? atol(argv[2]) : 2000;
   avdb_ctx ctx_store{};
   const avdb_ctx* ctx = &ctx_store;
@@ -100,17 +70,10 @@ int main(int argc, char** argv) {
   printf("export: %zu bytes, %llu rows, rc %d\n", text.size(), (unsigned long long)rows, rc);
   if (rc) return 1;
   const uint8_t bad[] = {'\t', '\r', '\n', '\'', '\\', 0x01, 0x7f, 0xc3, ':', 0};
-  long ok = 0;
-  for (long m = 0; m < mutations; ++m) {
-    // a window of the text, so a mutation costs little
-    const size_t len = text.size() < 4096 ? text.size() : 1 + rnd() % 4096;
-    const size_t at = text.size() > len ? rnd() % (text.size() - len) : 0;
-    std::vector<uint8_t> t(text.begin() + at, text.begin() + at + len);
-    for (int k = int(rnd() % 12); k > 0 && len; --k) t[rnd() % len] = bad[rnd() % sizeof bad];
-    size_t n_lines = count_lines(t.data(), t.size());
-    if (rnd() % 4 == 0) n_lines = rnd() % (t.size() + 2);  // (more lines than bytes is refused)
-    ok += run(ctx, t.data(), t.size(), n_lines, m % 2 == 1, &rows) == 0;
-  }
+  const long ok = mutate_windows(text, mutations, bad, sizeof bad,
+                                 [&](long m, const uint8_t* t, size_t bytes, size_t n_lines) {
+    return run(ctx, t, bytes, n_lines, m % 2 == 1, &rows) == 0;
+                                 });
   printf("%ld mutations, %ld with rc 0\nclean\n", mutations, ok);
   return 0;
 }

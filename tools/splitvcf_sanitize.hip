@@ -21,33 +21,9 @@
 // when done.
 #include "../annotatedvdb_amd/csrc/avdb_splitvcf.hip"
 
-#include <stdio.h>
-#include <stdlib.h>
+#include "sanitize_common.hpp"
 
-#include <memory>
 #include <string>
-
-void avdb_set_error(const char*, ...) {}
-namespace avdb {
-int text_line_starts(const uint8_t*, size_t, size_t, void*, uint64_t*, hipStream_t) { return AVDB_EHIP; }
-}  // namespace avdb
-
-static uint64_t g_seed = 0x9E3779B97F4A7C15ull;
-static uint64_t rnd() {
-  g_seed ^= g_seed << 13;
-  g_seed ^= g_seed >> 7;
-  g_seed ^= g_seed << 17;
-  return g_seed;
-}
-
-template <class T>
-static std::unique_ptr<T[]> exact(size_t n) { return std::unique_ptr<T[]>(new T[n ? n : 1]); }
-
-static size_t count_lines(const uint8_t* t, size_t n) {
-  size_t k = 0;
-  for (size_t i = 0; i < n; ++i) k += t[i] == '\n';
-  return k + (n && t[n - 1] != '\n');
-}
 
 // the host half of an avdb_chrom_map, filled as avdb_chrom_map_create fills it
 static void make_map(avdb_chrom_map* m, const std::vector<std::string>& keys, const std::vector<uint8_t>& codes) {
@@ -148,15 +124,7 @@ int main(int argc, char** argv) {
   }
   printf("%zu edge slabs, each without and with a map\n", slabs.size());
   if (argc > 1) {
-    text.clear();
-    FILE* f = fopen(argv[1], "rb");
-    if (!f) {
-      fprintf(stderr, "cannot read %s\n", argv[1]);
-      return 2;
-    }
-    uint8_t buf[65536];
-    for (size_t n; (n = fread(buf, 1, sizeof buf, f)) > 0;) text.insert(text.end(), buf, buf + n);
-    fclose(f);
+    text = read_file(argv[1]);
     const int rc = run(ctx, nullptr, text.data(), text.size(), count_lines(text.data(), text.size()), false, counts);
     printf("%s: %zu bytes, %llu comments, %llu unplaced lines, rc %d\n", argv[1], text.size(),
            (unsigned long long)counts[AVDB_SPLIT_COUNT_COMMENTS],
@@ -164,17 +132,10 @@ int main(int argc, char** argv) {
     if (rc) return 1;
   }
   const uint8_t bad[] = {'\t', '\t', ' ', '\r', '\n', '\n', '#', '1', '2', 'X', 'M', 'c', 0x1c, 0x1f, 0x85, 0xc2, 0xff, 0};
-  long ok = 0;
-  for (long m = 0; m < mutations; ++m) {
-    // a window of the text, so a mutation costs little
-    const size_t len = text.size() < 4096 ? text.size() : 1 + rnd() % 4096;
-    const size_t at = text.size() > len ? rnd() % (text.size() - len) : 0;
-    std::vector<uint8_t> t(text.begin() + at, text.begin() + at + len);
-    for (int k = int(rnd() % 12); k > 0 && len; --k) t[rnd() % len] = bad[rnd() % sizeof bad];
-    size_t n_lines = count_lines(t.data(), t.size());
-    if (rnd() % 4 == 0) n_lines = rnd() % (t.size() + 2);  // (more lines than bytes is refused)
-    ok += run(ctx, m % 3 ? nullptr : &map, t.data(), t.size(), n_lines, m % 2 == 1, counts) == 0;
-  }
+  const long ok = mutate_windows(text, mutations, bad, sizeof bad,
+                                 [&](long m, const uint8_t* t, size_t bytes, size_t n_lines) {
+    return run(ctx, m % 3 ? nullptr : &map, t, bytes, n_lines, m % 2 == 1, counts) == 0;
+                                 });
   printf("%ld mutations, %ld with rc 0\nclean\n", mutations, ok);
   return 0;
 }
