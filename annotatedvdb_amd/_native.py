@@ -75,6 +75,15 @@ CADDUPD_CHROM_MAX, CADDUPD_SCORE_MAX = 64, 24
 CADDUPD_COUNTS = ("rows", "skipped_lines", "skipped", "snv", "indel", "not_matched", "host_rows", "bad", "lone_cr",
                   "out_bytes")  # AVDB_CADDUPD_COUNT_*, by slot
 CADDUPD_N_COUNTS = len(CADDUPD_COUNTS)
+LOF_LINE_HOST, LOF_LINE_BAD, LOF_ROW_FIRST = 1, 2, 4  # AVDB_LOF_* entry and row flags
+LOF_COUNTS = ("rows", "lines", "comment_lines", "unannotated_lines", "no_values", "host_lines", "bad", "key_bytes",
+              "json_bytes", "lone_cr", "entries")  # AVDB_LOF_COUNT_*, by slot
+LOF_N_COUNTS = len(LOF_COUNTS)
+LOFUPD_BAD = 2  # AVDB_LOFUPD_BAD row flag
+LOFUPD_UPDATE_EXISTING = 1
+LOFUPD_COUNTS = ("rows", "skipped_lines", "skipped", "not_annotated", "bad", "out_bytes",
+                 "lone_cr")  # AVDB_LOFUPD_COUNT_*, by slot
+LOFUPD_N_COUNTS = len(LOFUPD_COUNTS)
 EXPVCF_ROW_HOST, EXPVCF_BAD, EXPVCF_DROPPED = 1, 2, 4  # AVDB_EXPVCF_* row flags
 EXPVCF_STREAM_VCF, EXPVCF_STREAM_INVALID = 0, 1
 EXPVCF_COUNTS = ("valid", "invalid", "skipped_lines", "filtered", "bad", "lone_cr", "vcf_bytes",
@@ -123,6 +132,19 @@ class CaddTableView(ctypes.Structure):
         super().__init__(ctypes.sizeof(CaddTableView), 0, n_rows, text, text_bytes, *columns)
 
 
+class LofTableView(ctypes.Structure):
+    """avdb_lof_table (include/avdb.h); ``struct_size`` is filled in."""
+    _fields_ = [("struct_size", ctypes.c_uint32), ("reserved", ctypes.c_uint32), ("n_rows", ctypes.c_uint64),
+                ("keys", ctypes.c_void_p), ("key_off", ctypes.c_void_p), ("keyset", ctypes.c_void_p),
+                ("keyset_bytes", ctypes.c_uint64), ("json", ctypes.c_void_p), ("json_bytes", ctypes.c_uint64),
+                ("json_off", ctypes.c_void_p), ("json_len", ctypes.c_void_p), ("hit", ctypes.c_void_p)]
+
+    def __init__(self, n_rows: int = 0, keys=None, key_off=None, keyset=None, keyset_bytes: int = 0, json=None,
+                 json_bytes: int = 0, json_off=None, json_len=None, hit=None):
+        super().__init__(ctypes.sizeof(LofTableView), 0, n_rows, keys, key_off, keyset, keyset_bytes, json, json_bytes,
+                         json_off, json_len, hit)
+
+
 class LineResult(ctypes.Structure):
     """avdb_line_result (include/avdb.h)."""
     _fields_ = [(name, ctypes.c_uint32) for name in ("state", "flags", "copy_bytes", "map_bytes", "n_rec", "n_rows",
@@ -143,7 +165,7 @@ EXPORTED_SYMBOLS = [
     "avdb_chrom_map_create", "avdb_chrom_map_destroy",
     "avdb_format_workspace_size", "avdb_vcf_format_size", "avdb_vcf_format_write", "avdb_vcf_line_host",
     "avdb_display_attributes",
-    "avdb_keyset_workspace_size", "avdb_keyset_build", "avdb_keyset_probe",
+    "avdb_keyset_workspace_size", "avdb_keyset_build", "avdb_keyset_build_host", "avdb_keyset_probe",
     "avdb_primary_keys", "avdb_keyset_probe_text", "avdb_primary_keys_bound",
     "avdb_primary_keys_onepass_workspace_size", "avdb_primary_keys_onepass", "avdb_primary_keys_onepass_ex",
     "avdb_primary_keys_fill_digests",
@@ -165,6 +187,10 @@ EXPORTED_SYMBOLS = [
     "avdb_export_vcf_size_host", "avdb_export_vcf_write_host",
     "avdb_vcf_split_workspace_size", "avdb_vcf_split_size", "avdb_vcf_split_write",
     "avdb_vcf_split_size_host", "avdb_vcf_split_write_host",
+    "avdb_lof_table_workspace_size", "avdb_lof_table_size", "avdb_lof_table_write",
+    "avdb_lof_table_size_host", "avdb_lof_table_write_host",
+    "avdb_lof_update_workspace_size", "avdb_lof_update_size", "avdb_lof_update_write",
+    "avdb_lof_update_size_host", "avdb_lof_update_write_host",
 ]
 
 
@@ -256,6 +282,7 @@ def _sig(lib):
     f.avdb_display_attributes.argtypes = [P, P, P, P, P, P, P, P, SZ, SZ, P, SZ, P, P, P, P]
     f.avdb_keyset_workspace_size.argtypes = [SZ, ctypes.POINTER(SZ)]
     f.avdb_keyset_build.argtypes = [P, P, P, SZ, P, SZ, P]
+    f.avdb_keyset_build_host.argtypes = [P, P, P, SZ, P, SZ]
     f.avdb_keyset_probe.argtypes = [P, P, SZ, P, P, SZ, P, P, P, P, P, P, SZ, SZ, I32, P, P, P, P]
     f.avdb_primary_keys.argtypes = [P, P, P, P, P, P, P, SZ, P, P, P, SZ, U32, P, SZ, P, P, P, SZ, P, SZ, P, P]
     f.avdb_primary_keys_onepass.argtypes = list(f.avdb_primary_keys.argtypes)  # same signature
@@ -318,6 +345,17 @@ def _sig(lib):
     f.avdb_vcf_split_size.argtypes = f.avdb_vcf_split_size_host.argtypes + [P, SZ, P]
     f.avdb_vcf_split_write_host.argtypes = [P, P, SZ, SZ, P, P, P, P, SZ, P, P, P]
     f.avdb_vcf_split_write.argtypes = f.avdb_vcf_split_write_host.argtypes + [P, SZ, P]
+    LT = ctypes.POINTER(LofTableView)
+    f.avdb_lof_table_workspace_size.argtypes = [SZ, SZ, ctypes.POINTER(SZ)]
+    f.avdb_lof_table_size_host.argtypes = [P, P, SZ, SZ] + [P] * 6
+    f.avdb_lof_table_size.argtypes = f.avdb_lof_table_size_host.argtypes + [P, SZ, P]
+    f.avdb_lof_table_write_host.argtypes = [P, P, SZ, SZ, SZ, SZ, P, P, P, P, P, P, SZ, P, P, SZ, P, P, P, P, P]
+    f.avdb_lof_table_write.argtypes = f.avdb_lof_table_write_host.argtypes + [P, SZ, P]
+    f.avdb_lof_update_workspace_size.argtypes = [SZ, SZ, ctypes.POINTER(SZ)]
+    f.avdb_lof_update_size_host.argtypes = [P, P, SZ, SZ, LT, U32, U32, P, P, P, P, P, P]
+    f.avdb_lof_update_size.argtypes = f.avdb_lof_update_size_host.argtypes + [P, SZ, P]
+    f.avdb_lof_update_write_host.argtypes = [P, P, SZ, SZ, SZ, LT, P, P, P, P, P, P, SZ, P, P]
+    f.avdb_lof_update_write.argtypes = f.avdb_lof_update_write_host.argtypes + [P, SZ, P]
     for name in EXPORTED_SYMBOLS:
         if name not in ("avdb_last_error",):
             getattr(f, name).restype = I32

@@ -14,35 +14,15 @@
 //                    id "chrom:pos:ref:alt" generated on the fly (never
 //                    materialised), byte-exact confirmation against the key; with
 //                    check_alt, a miss retries "chrom:pos:alt:ref" (alleles switched)
-#include "avdb_internal.hpp"
+// The hash, the insert and the text probe are avdb_keyset.hpp, shared with K16b and the host entry.
+#include "avdb_keyset.hpp"
+
+#include <string.h>
 
 namespace avdb {
 
-__device__ __forceinline__ uint64_t mix(uint64_t x) {
-  x ^= x >> 33;
-  x *= 0xff51afd7ed558ccdull;
-  x ^= x >> 33;
-  x *= 0xc4ceb9fe1a85ec53ull;
-  x ^= x >> 33;
-  return x;
-}
-
-// streaming hash of a byte sequence: bytes packed little-endian into 8-byte
-// words, each completed word mixed in; the length closes it.  Keys and
-// generated metaseq ids go through the same byte stream, so equal strings hash
-// equal however they are assembled.
-struct Hasher {
-  uint64_t h = 0x9E3779B97F4A7C15ull, w = 0;
-  uint32_t n = 0;
-  __device__ __forceinline__ void put(uint32_t c) {
-    w |= uint64_t(c & 0xFFu) << (8 * (n & 7));
-    if ((++n & 7) == 0) { h = mix(h ^ w); w = 0; }
-  }
-  __device__ __forceinline__ uint64_t done() const {
-    const uint64_t x = mix(h ^ w ^ (uint64_t(n) << 56));
-    return x ? x : 1ull;  // 0 marks an empty slot
-  }
-};
+using keyset::Hasher;
+using keyset::mix;
 
 // "chrom:pos:" of a record (<= 16 bytes); contig labels of chromosomes.py:9-38
 __device__ __forceinline__ uint32_t metaseq_prefix(uint32_t c, uint32_t pos, uint8_t* b) {
@@ -93,17 +73,8 @@ __global__ __launch_bounds__(kBlock) void k_keyset_insert(const uint8_t* __restr
                                                           const uint64_t* __restrict__ key_off, size_t n,
                                                           unsigned long long* __restrict__ tkey,
                                                           uint32_t* __restrict__ tidx, uint64_t mask) {
-  for (size_t i = size_t(blockIdx.x) * blockDim.x + threadIdx.x; i < n; i += size_t(gridDim.x) * blockDim.x) {
-    Hasher hs;
-    for (uint64_t b = key_off[i]; b < key_off[i + 1]; ++b) hs.put(keys[b]);
-    const uint64_t h = hs.done();
-    uint64_t slot = mix(h ^ 0x5bd1e995ull) & mask;
-    for (;;) {  // >= 2n slots: terminates
-      const unsigned long long prev = atomicCAS(&tkey[slot], 0ull, (unsigned long long)h);
-      if (prev == 0ull || prev == h) { atomicMin(&tidx[slot], uint32_t(i)); break; }
-      slot = (slot + 1) & mask;
-    }
-  }
+  for (size_t i = size_t(blockIdx.x) * blockDim.x + threadIdx.x; i < n; i += size_t(gridDim.x) * blockDim.x)
+    keyset::insert(keys, key_off, i, tkey, tidx, mask);
 }
 
 // first key equal to pre+x+':'+y, or -1; *coll counts 64-bit hash collisions
@@ -168,13 +139,6 @@ __global__ __launch_bounds__(kBlock) void k_keyset_probe(
 // K6 over arbitrary strings (e.g. the primary keys K7 rendered): one lane per
 // query string q[q_off[i] .. q_off[i+1]) (skipped where skip[i] != 0);
 // match[i] = index of the first equal key, or -1
-__device__ __forceinline__ bool str_equals(const uint8_t* a, uint64_t alen, const uint8_t* b, uint64_t blen) {
-  if (alen != blen) return false;
-  for (uint64_t i = 0; i < alen; ++i)
-    if (a[i] != b[i]) return false;
-  return true;
-}
-
 __global__ __launch_bounds__(kBlock) void k_keyset_probe_text(
     const uint8_t* __restrict__ keys, const uint64_t* __restrict__ key_off, size_t n_keys,
     const unsigned long long* __restrict__ tkey, const uint32_t* __restrict__ tidx, uint64_t mask,
@@ -183,30 +147,8 @@ __global__ __launch_bounds__(kBlock) void k_keyset_probe_text(
   uint32_t hits = 0, coll = 0;
   for (size_t i = size_t(blockIdx.x) * blockDim.x + threadIdx.x; i < n; i += size_t(gridDim.x) * blockDim.x) {
     int32_t m = -1;
-    if (!skip || !skip[i]) {
-      const uint8_t* s = q + q_off[i];
-      const uint64_t len = q_off[i + 1] - q_off[i];
-      Hasher hs;
-      for (uint64_t b = 0; b < len; ++b) hs.put(s[b]);
-      const uint64_t h = hs.done();
-      uint64_t slot = mix(h ^ 0x5bd1e995ull) & mask;
-      for (;;) {
-        const unsigned long long t = tkey[slot];
-        if (t == 0ull) break;
-        if (t == h) {
-          const uint32_t k = tidx[slot];
-          if (str_equals(keys + key_off[k], key_off[k + 1] - key_off[k], s, len)) {
-            m = int32_t(k);
-          } else {  // a different key with the same 64-bit hash: exact scan
-            ++coll;
-            for (size_t j = 0; j < n_keys && m < 0; ++j)
-              if (str_equals(keys + key_off[j], key_off[j + 1] - key_off[j], s, len)) m = int32_t(j);
-          }
-          break;
-        }
-        slot = (slot + 1) & mask;
-      }
-    }
+    if (!skip || !skip[i])
+      m = keyset::probe_text(keys, key_off, n_keys, tkey, tidx, mask, q + q_off[i], q_off[i + 1] - q_off[i], &coll);
     match[i] = m;
     hits += m >= 0;
   }
@@ -220,11 +162,7 @@ __global__ __launch_bounds__(kBlock) void k_keyset_probe_text(
 
 using namespace avdb;
 
-static uint64_t keyset_slots(size_t n) {
-  uint64_t s = 1024;
-  while (s < 2ull * n) s <<= 1;
-  return s;
-}
+static uint64_t keyset_slots(size_t n) { return keyset::slots(n); }
 
 extern "C" int avdb_keyset_workspace_size(size_t n_keys, size_t* bytes) {
   if (!bytes) return AVDB_EINVAL;
@@ -317,5 +255,29 @@ extern "C" int avdb_keyset_probe_text(avdb_ctx* ctx, const void* table, size_t t
                      static_cast<hipStream_t>(stream), keys, key_off, n_keys, tkey, tidx, slots - 1, q, q_off, skip,
                      n, match, reinterpret_cast<unsigned long long*>(counters));
   AVDB_LAUNCH_CHECK("k_keyset_probe_text");
+  return AVDB_OK;
+}
+
+// the same table built on the host: it answers every probe as the device's does (the first of
+// equal keys), though not necessarily slot for slot
+extern "C" int avdb_keyset_build_host(const avdb_ctx* ctx, const uint8_t* keys, const uint64_t* key_off, size_t n_keys,
+                                      void* table, size_t table_bytes) {
+  if (!ctx || !key_off || !table || (n_keys && !keys)) {
+    avdb_set_error("avdb_keyset_build_host: null argument");
+    return AVDB_EINVAL;
+  }
+  if (n_keys >= 0x7FFFFFFFull) { avdb_set_error("avdb_keyset_build_host: too many keys"); return AVDB_EINVAL; }
+  size_t need = 0;
+  avdb_keyset_workspace_size(n_keys, &need);
+  if (table_bytes < need) {
+    avdb_set_error("avdb_keyset_build_host: table of %zu bytes required", need);
+    return AVDB_ERANGE;
+  }
+  const uint64_t slots = keyset_slots(n_keys);
+  auto* tkey = static_cast<unsigned long long*>(table);
+  auto* tidx = reinterpret_cast<uint32_t*>(tkey + slots);
+  memset(tkey, 0, slots * 8);
+  memset(tidx, 0xFF, slots * 4);
+  for (size_t i = 0; i < n_keys; ++i) keyset::insert(keys, key_off, i, tkey, tidx, slots - 1);
   return AVDB_OK;
 }

@@ -133,6 +133,55 @@ class CaddUpdateRows:
     counts: Dict[str, int]
 
 
+@dataclass
+class LofTable:
+    """What K16a makes of the VCF SnpEff wrote (:meth:`Engine.lof_table_build`): one row per
+    ALT allele of every line that carries a LOF or NMD value.  Row ``k``'s lookup id
+    ``chrom:pos:ref:alt`` is ``keys[key_off[k]:key_off[k + 1]]``; ``rkeys`` / ``rkey_off`` hold
+    the same keys in reverse row order and ``keyset`` the K6 hash table over them (its first of
+    equal keys is the last annotated record of an id); ``json[json_off[k]:json_off[k] +
+    json_len[k]]`` is the row's line's ``json.dumps({'LOF': [...], 'NMD': [...]})`` (the alts of
+    a line share one span); ``line_start`` the row's line's offset in ``text``; ``flags`` the
+    rows' ``N.LOF_*`` flags; ``hit[k]`` becomes 1 when an export row matches row ``k``
+    (:meth:`Engine.lof_update_rows`); ``counts`` the build's counts by name (``N.LOF_COUNTS``)."""
+    engine: object
+    text: torch.Tensor
+    n_rows: int
+    keys: torch.Tensor
+    key_off: torch.Tensor
+    rkeys: torch.Tensor
+    rkey_off: torch.Tensor
+    keyset: torch.Tensor
+    json: torch.Tensor
+    json_off: torch.Tensor
+    json_len: torch.Tensor
+    line_start: torch.Tensor
+    flags: torch.Tensor
+    hit: torch.Tensor
+    counts: Dict[str, int]
+
+    def view(self) -> "N.LofTableView":
+        """The C struct over these tensors (valid while they are alive)."""
+        if self.n_rows == 0:
+            return N.LofTableView()
+        return N.LofTableView(self.n_rows, N.ptr(self.rkeys), N.ptr(self.rkey_off), N.ptr(self.keyset),
+                              self.keyset.numel(), N.ptr(self.json), self.json.numel(), N.ptr(self.json_off),
+                              N.ptr(self.json_len), N.ptr(self.hit))
+
+
+@dataclass
+class LofUpdateRows:
+    """What K16b makes of an export of ``AnnotatedVDB.Variant`` (:meth:`Engine.lof_update_rows`):
+    ``text`` holds the ``n`` update rows (``pk<TAB>chr<label><TAB>json<LF>``, row ``i`` at
+    ``row_off[i] .. row_off[i + 1]``), ``match`` the table row each was rendered from,
+    ``counts`` the pass's counts by name (``N.LOFUPD_COUNTS``)."""
+    n: int
+    text: torch.Tensor
+    row_off: torch.Tensor
+    match: torch.Tensor
+    counts: Dict[str, int]
+
+
 VCF_EXPORT_HEADER = b"#CHRM\tPOS\tID\tREF\tALT\tQUAL\tFILTER\tINFO\n"  # (sic) export_variant2vcf.py:26
 
 
@@ -1400,6 +1449,18 @@ class Engine:
         self._launch("avdb_keyset_build", keys if keys.numel() else None, key_off, n, table, table.numel())
         return table
 
+    def keyset_table(self, keys: torch.Tensor, key_off: torch.Tensor) -> torch.Tensor:
+        """:meth:`keyset_build` where the engine lives: on a host-only engine the library's
+        ``avdb_keyset_build_host`` builds the table (it answers every probe as the device's
+        does, though not necessarily slot for slot)."""
+        if not self.host_only:
+            return self.keyset_build(keys, key_off)
+        keys, key_off = self._dev(keys), self._dev(key_off)
+        n = key_off.numel() - 1
+        table = self.empty(N.size("avdb_keyset_workspace_size", n), torch.uint8)
+        self._call("avdb_keyset_build_host", keys if keys.numel() else None, key_off, n, table, table.numel())
+        return table
+
     def keyset_probe(self, table: torch.Tensor, keys: torch.Tensor, key_off: torch.Tensor, b: RecordBatch,
                      check_alt: bool = True, counters: Optional[torch.Tensor] = None):
         """``(match int32[n], kind uint8[n])``: first equal key of each record's
@@ -1485,6 +1546,44 @@ class Engine:
         ``buffer_variants`` itself and copied into their spans after the write pass.
         On a host-only engine the library's host entries run the same per-line code."""
         return slab_passes.cadd_update_rows(self, text, snv, indel, chromosome, skip_existing, contigs)
+
+    # -- K16: SnpEff LOF/NMD update rows ---------------------------------------------
+    def lof_table_build(self, text) -> "LofTable":
+        """K16a: a '\\n'-separated slab of the VCF SnpEff wrote (bytes, numpy ``uint8`` or a
+        ``uint8`` tensor) -> :class:`LofTable` on this engine's device.  A line is read as
+        ``load_annotation`` (``load_snpeff_lof.py:250-288``) reads it: ``rstrip()``ped; ``#``
+        lines are comments; a line without ``;LOF=`` and ``;NMD=`` anywhere in it is
+        unannotated; INFO is then looked up by key (the last item of a key wins) and a line
+        with neither value counts ``no_values``.  Every other line gives one row per ALT
+        allele, keyed ``chrom:pos:ref:alt`` (CHROM without ``chr``, ``MT`` as ``M``,
+        ``str(int(POS))``), and one JSON text.  Of an id the VCF repeats the last record
+        answers a probe (the reference keeps the last within one ``--numLookups`` batch).
+        Lines outside the device subset (``host_lines``: DESIGN.md, K16) are rendered by
+        :func:`annotatedvdb_amd.snpeff_lof.annotated_line` and copied into their spans after
+        the write pass; an exception it raises is re-raised with the line number attached
+        (``err.line``, 1-based, and a note).  A carriage return inside a line raises
+        ``ValueError``.  Three syncs: the line count, the size pass's counts, the end.  On a
+        host-only engine the library's host entries run the same per-line code."""
+        return slab_passes.lof_table_build(self, text)
+
+    def lof_update_rows(self, text, table: "LofTable", update_existing: bool = False,
+                        contigs=None) -> "LofUpdateRows":
+        """K16b: a slab of an export
+        ``record_primary_key<TAB>metaseq_id<TAB>loss_of_function[<TAB>...]`` (K13's
+        conventions: header line, ``\\r\\n``, fewer than two fields counted ``skipped_lines``,
+        ``contigs``, a metaseq id without four parts raises) streamed against a
+        :class:`LofTable` -> :class:`LofUpdateRows`: for every export row whose metaseq id
+        is annotated the tuple ``__buffer_update_values`` appends
+        (``vcf_variant_loader.py:197-217``) as ``pk<TAB>chr<label><TAB>json<LF>``, in export
+        order; two primary keys of one variant both get a row (the reference's
+        ``firstHitOnly=False`` lookup).  An id the table does not hold is counted
+        ``not_annotated``; an annotated record whose third column is not NULL (``\\N``,
+        empty or absent) is counted ``skipped`` and gets no row unless ``update_existing``
+        (where the reference itself raises).  ``table.hit`` records the table
+        rows matched, skipped records included.  Rows come out in export order.  Three syncs:
+        the line count, the size pass's counts, the end.  On a host-only engine the library's
+        host entries run the same per-line code."""
+        return slab_passes.lof_update_rows(self, text, table, update_existing, contigs)
 
     # -- K14: the VCF files of an export ------------------------------------------
     def export_vcf(self, text, contigs=None, variants_per_file: int = 10_000_000) -> "ExportVcf":

@@ -33,8 +33,10 @@ variant_loader.py:395-405,479-486 do (``copy_expert(copy_sql, buffer, 2**10)``,
 then a fresh buffer), ``update_variants`` hands the update buffer over as
 :457-476 do, and ``set_algorithm_invocation`` takes the AlgorithmInvocation id
 from a provider the caller installs (``set_algorithm_invocation_provider``) in
-place of the row insert (:431-437).  ``update_existing`` (rewriting loaded rows)
-stays out of scope and raises ``NotImplementedError``.  The ADSP datasource checks
+place of the row insert (:431-437).  ``update_existing`` (rewriting loaded rows
+line by line through a lookup) raises ``NotImplementedError``; the update passes work
+from an export of the table instead: ``cadd_scores`` in :mod:`annotatedvdb_amd.cadd`,
+``loss_of_function`` in :mod:`annotatedvdb_amd.snpeff_lof`.  The ADSP datasource checks
 every alt's primary key against the rows already loaded (``is_duplicate(recordPK)``,
 vcf_variant_loader.py:303-307) through the same exported key set (K7 keys, K6
 text probe): a loaded key becomes an ``is_adsp_variant`` update in
@@ -331,7 +333,9 @@ class VCFVariantLoader(object):
 
     def set_update_existing(self, updateExisting):
         if updateExisting:
-            raise NotImplementedError("updating existing rows needs the database; out of scope")
+            raise NotImplementedError("updating existing rows line by line needs the database's lookup; the update "
+                                      "passes take an export of the table instead (loss_of_function: "
+                                      "annotatedvdb_amd.snpeff_lof / load_snpeff_lof, cadd_scores: annotatedvdb_amd.cadd)")
 
     def update_existing(self):
         return self._update_existing

@@ -1,6 +1,6 @@
 """The passes over a '\\n'-separated text slab behind :class:`~annotatedvdb_amd.engine.Engine`:
 K10a ``cadd_table_build``, K12 ``existing_table_build``, K13 ``cadd_update_rows``, K14
-``export_vcf`` and K15 ``split_vcf``.
+``export_vcf``, K15 ``split_vcf`` and K16 ``lof_table_build`` / ``lof_update_rows``.
 
 The two-pass ones have one shape: line count -> size pass -> its counts to the host (second
 sync) -> the rows the device leaves to the host rendered here -> outputs allocated -> write
@@ -375,3 +375,112 @@ def split_vcf(engine, text, chrom_map=None, unknown: str = "raise"):
     sp.check_totals("avdb_vcf_split_write", end[0:2], total, "lines")
     cnt = {"lines": n_of, "bytes": b_of, "comments": comments, "host_lines": host_lines}
     return E.SplitVcf(out[:total], [int(x) for x in end[2:]], cnt, first_other)
+
+
+def _line_number(sp: SlabPass, offset: int) -> int:
+    """The 1-based number of the line that starts at ``offset``."""
+    return int((sp.text[:offset] == 10).sum()) + 1
+
+
+def lof_table_build(engine, text):
+    from .snpeff_lof import annotated_line
+    sp = SlabPass(engine, text, "lof_table", "avdb_lof_table_workspace_size")
+    ent_start, ent_alts, ent_key, ent_json, ent_flags = sp.cols(torch.int64, torch.int32, torch.int32, torch.int32,
+                                                                torch.uint8)
+    ents = (ent_start, ent_alts, ent_key, ent_json, ent_flags)
+    counts = engine.empty(N.LOF_N_COUNTS, torch.int64)
+    sp.call("avdb_lof_table_size", sp.tp, sp.nb, sp.n_lines, *ents, counts)
+    cnt = sp.counts(counts, N.LOF_COUNTS)
+    if cnt["lone_cr"]:
+        raise ValueError(f"{cnt['lone_cr']} carriage return(s) inside lines of the VCF: Python's text mode ends a "
+                         "line there and the device pass does not")
+    ne = cnt["entries"]
+    host = None
+    if cnt["host_lines"]:
+        # the lines outside the device subset: their text to the host, rendered in file order
+        host = torch.nonzero(ent_flags[:ne] & N.LOF_LINE_HOST).flatten()
+        host_keys, host_json = [], []
+        for at, b in zip(ent_start[host].tolist(), sp.rows_bytes(ent_start[host], _lines_to_next(sp, host, ent_start, ne))):
+            try:
+                keys, js = annotated_line(b.split(b"\n", 1)[0])
+            except Exception as err:
+                err.line = _line_number(sp, at)
+                if hasattr(err, "add_note"):
+                    err.add_note(f"line {err.line} of the VCF")
+                raise
+            if not js:  # neither value: the line contributes nothing
+                keys = []
+                cnt["no_values"] += 1
+            host_keys.append(keys)
+            host_json.append(js)
+        alts = [len(k) for k in host_keys]
+        kb = [sum(map(len, k)) for k in host_keys]
+        cnt["rows"] += sum(alts)
+        cnt["key_bytes"] += sum(kb)
+        cnt["json_bytes"] += sum(map(len, host_json))
+        ent_alts[host] = torch.tensor(alts, dtype=torch.int32).to(engine.device)
+        ent_key[host] = torch.tensor(kb, dtype=torch.int32).to(engine.device)
+        ent_json[host] = sp.lengths(host_json).to(torch.int32)
+    n, key_bytes, json_bytes = cnt["rows"], cnt["key_bytes"], cnt["json_bytes"]
+    keys = engine.empty(max(1, key_bytes), torch.uint8)
+    json_blob = engine.empty(max(1, json_bytes), torch.uint8)
+    key_off = engine.empty(n + 1, torch.int64)
+    json_off, line_start = (engine.empty(max(1, n), torch.int64) for _ in range(2))
+    json_len = engine.empty(max(1, n), torch.int32)
+    flags = engine.empty(max(1, n), torch.uint8)
+    totals = engine.empty(4, torch.int64)
+    sp.call("avdb_lof_table_write", sp.tp, sp.nb, sp.n_lines, ne, n, *ents, keys, key_bytes, key_off, json_blob,
+            json_bytes, json_off, json_len, line_start, flags, totals)
+    if host is not None and host.numel():
+        def starts(lengths):  # where each entry's share of a blob (or its rows) begins
+            return torch.cumsum(lengths[:ne].long(), 0) - lengths[:ne].long()
+        koff, joff, roff = (starts(x)[host] for x in (ent_key, ent_json, ent_alts))
+        sp.splice(keys, koff, [b"".join(k) for k in host_keys])
+        sp.splice(json_blob, joff, host_json)
+        rows_at, offs = [], []
+        for first, base, ks in zip(roff.tolist(), koff.tolist(), host_keys):
+            for a, k in enumerate(ks):
+                rows_at.append(first + a)
+                offs.append(base)
+                base += len(k)
+        if rows_at:
+            key_off[torch.tensor(rows_at, dtype=torch.int64).to(engine.device)] = \
+                torch.tensor(offs, dtype=torch.int64).to(engine.device)
+    got = totals.cpu().tolist()
+    if got[3] or got[:3] != [key_bytes, json_bytes, n]:
+        raise N.NativeError("avdb_lof_table_write" + sp.suffix, N.AVDB_ERANGE,
+                            f"totals {got[:3]} do not fit the sizes the size pass gave")
+    # K6 keeps the first of equal keys: over the keys in reverse row order that is the last record of an id
+    lens = (key_off[1:] - key_off[:-1]).flip(0)
+    rkey_off = torch.cat([torch.zeros(1, dtype=torch.int64, device=engine.device), torch.cumsum(lens, 0)])
+    rkeys = keys[engine._spans(key_off[:-1].flip(0), lens)] if n else keys[:0]
+    keyset = engine.keyset_table(rkeys, rkey_off)
+    hit = torch.zeros(max(1, n), dtype=torch.uint8, device=engine.device)
+    return E.LofTable(engine, sp.text, n, keys[:key_bytes], key_off, rkeys, rkey_off, keyset, json_blob[:json_bytes],
+                      json_off[:n], json_len[:n], line_start[:n], flags[:n], hit[:n] if n else hit[:0], cnt)
+
+
+def lof_update_rows(engine, text, table, update_existing: bool = False, contigs=None):
+    if table.text.device != engine.device:
+        raise ValueError("LOF table lives on another device than this engine")
+    view = table.view()
+    vp = ctypes.byref(view)
+    sp = SlabPass(engine, text, "lof_update", "avdb_lof_update_workspace_size")
+    row_start, pk_len, match, out_len, flags = sp.cols(torch.int64, torch.int32, torch.int32, torch.int32, torch.uint8)
+    counts = engine.empty(N.LOFUPD_N_COUNTS, torch.int64)
+    sp.call("avdb_lof_update_size", sp.tp, sp.nb, sp.n_lines, vp, E.existing_contig_mask(contigs),
+            N.LOFUPD_UPDATE_EXISTING if update_existing else 0, row_start, pk_len, match, out_len, flags, counts)
+    cnt = sp.counts(counts, N.LOFUPD_COUNTS)
+    if cnt["lone_cr"]:
+        sp.raise_lone_cr(cnt["lone_cr"], "pass does not")
+    n = cnt["rows"]
+    if cnt["bad"]:
+        sp.raise_bad_metaseq(row_start, flags, N.LOFUPD_BAD, n, cnt["bad"])
+    out_bytes = cnt["out_bytes"]
+    out_text = engine.empty(max(1, out_bytes), torch.uint8)
+    row_off = engine.empty(n + 1, torch.int64)
+    totals = engine.empty(2, torch.int64)
+    sp.call("avdb_lof_update_write", sp.tp, sp.nb, sp.n_lines, n, vp, row_start, pk_len, match, out_len, flags,
+            out_text, out_bytes, row_off, totals)
+    sp.check_totals("avdb_lof_update_write", totals.cpu().tolist(), out_bytes, "rows")
+    return E.LofUpdateRows(n, out_text[:out_bytes], row_off, match[:n], cnt)

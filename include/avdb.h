@@ -685,6 +685,10 @@ int avdb_host_free(void* ptr);
 int avdb_keyset_workspace_size(size_t n_keys, size_t* bytes);
 int avdb_keyset_build(avdb_ctx* ctx, const uint8_t* keys, const uint64_t* key_off, size_t n_keys, void* table,
                       size_t table_bytes, void* stream);
+/* the same table built on the host (host arrays): it answers every probe as avdb_keyset_build's
+ * does, though not necessarily slot for slot */
+int avdb_keyset_build_host(const avdb_ctx* ctx, const uint8_t* keys, const uint64_t* key_off, size_t n_keys,
+                           void* table, size_t table_bytes);
 int avdb_keyset_probe(avdb_ctx* ctx, const void* table, size_t table_bytes, const uint8_t* keys,
                       const uint64_t* key_off, size_t n_keys, const uint8_t* chrom, const uint32_t* pos,
                       const uint64_t* allele_off, const uint32_t* ref_len, const uint32_t* alt_len,
@@ -1202,6 +1206,122 @@ int avdb_hist_allgather_workspace_size(int world, size_t n_bins, size_t n_counte
 int avdb_hist_allgather(avdb_ctx* ctx, void* comm, const uint32_t* hist, size_t n_bins,
                         const uint64_t* counters, size_t n_counters, uint32_t* node_hist,
                         uint64_t* node_counters, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---- K16: SnpEff LOF/NMD update rows (Load/bin/load_snpeff_lof.py) ---------
+ * K16a, the table: `text` is a '\n'-separated slab of the VCF SnpEff wrote.  A line is read
+ * as load_annotation reads it (:250-288): rstrip()ped; a '#' line is a comment; a line
+ * without ';LOF=' and ';NMD=' anywhere in it is unannotated; of the others INFO is looked up
+ * by key (the last item of a key wins), and a line with neither key counts no_values.  Every
+ * other line is an entry: it yields one table row per ALT allele, the lookup id
+ * chrom:pos:ref:alt (CHROM without `chr`, MT as M, POS without leading zeros) as the row's
+ * key, and one JSON text, json.dumps({'LOF': [...], 'NMD': [...]}) of
+ * parse_annotation_string's lists, shared by the line's rows.  An entry outside the device
+ * subset is flagged AVDB_LOF_LINE_HOST: no rows, keys or JSON are counted
+ * for it, the caller renders it, patches its alts / key_bytes / json_len and copies its
+ * bytes into the spans the write pass leaves blank; AVDB_LOF_LINE_BAD marks the host lines
+ * with fewer than eight fields.  A '\r' inside a stripped line is counted
+ * (AVDB_LOF_COUNT_LONE_CR).
+ *   1. avdb_lof_table_size: per entry (n_lines entries allocated, counts[ENTRIES] written)
+ *      its line's offset, alts, key bytes, JSON length and flags; counts
+ *      (AVDB_LOF_N_COUNTS x u64, set by the call).
+ *   2. avdb_lof_table_write (n_entries as counted, n_rows = the sum of ent_alts, the same
+ *      text): keys (key_cap bytes) with key_off[n_rows + 1], json (json_cap bytes), and per
+ *      row the span of its line's JSON (row_json_off / row_json_len), its line's offset
+ *      and flags (AVDB_LOF_ROW_FIRST on a line's first row, AVDB_LOF_LINE_HOST on a host
+ *      line's rows, whose key_off all hold the line's first key's offset).  totals[0 .. 2]:
+ *      the key bytes, JSON bytes and rows the entries add up to; totals[3]: 1 when any of
+ *      them exceeds its capacity (nothing is written then; the _host form returns
+ *      AVDB_ERANGE).  keys and json must be 8-byte aligned.
+ * K16b, the update rows: `text` is a slab of an export
+ * record_primary_key<TAB>metaseq_id<TAB>loss_of_function[<TAB>...] read by K13's conventions
+ * (header line, fewer than two fields, contig mask, "\r\n", lone '\r').  A metaseq id
+ * without exactly three ':' is a row flagged AVDB_LOFUPD_BAD (no output); the id's bytes are
+ * probed in the table's key set: no hit counts NOT_ANNOTATED and is no row; a hit on row t
+ * stores 1 to table->hit[t] and, unless the line's third field is present and neither empty
+ * nor `\N` (counted SKIPPED, no row, without AVDB_LOFUPD_UPDATE_EXISTING), is the row
+ * pk<TAB>chr<label of the metaseq id><TAB>json of t<LF>.
+ * avdb_lof_table: the key set (avdb_keyset_build) is over the keys in REVERSE row order
+ * (key i is row n_rows - 1 - i), so the last annotated record of an id answers.
+ * Workspaces: avdb_lof_table_workspace_size / avdb_lof_update_workspace_size bytes, 256-byte
+ * aligned; the device entries enqueue on `stream`, the _host forms run the same per-line code
+ * on host arrays. */
+#define AVDB_LOF_LINE_HOST 0x01u
+#define AVDB_LOF_LINE_BAD 0x02u
+#define AVDB_LOF_ROW_FIRST 0x04u
+#define AVDB_LOF_COUNT_ROWS 0
+#define AVDB_LOF_COUNT_LINES 1
+#define AVDB_LOF_COUNT_COMMENT_LINES 2
+#define AVDB_LOF_COUNT_UNANNOTATED_LINES 3
+#define AVDB_LOF_COUNT_NO_VALUES 4
+#define AVDB_LOF_COUNT_HOST_LINES 5
+#define AVDB_LOF_COUNT_BAD 6
+#define AVDB_LOF_COUNT_KEY_BYTES 7
+#define AVDB_LOF_COUNT_JSON_BYTES 8
+#define AVDB_LOF_COUNT_LONE_CR 9
+#define AVDB_LOF_COUNT_ENTRIES 10
+#define AVDB_LOF_N_COUNTS 11
+#define AVDB_LOFUPD_BAD 0x02u
+#define AVDB_LOFUPD_UPDATE_EXISTING 0x01u /* avdb_lof_update_size's flags */
+#define AVDB_LOFUPD_COUNT_ROWS 0
+#define AVDB_LOFUPD_COUNT_SKIPPED_LINES 1
+#define AVDB_LOFUPD_COUNT_SKIPPED 2
+#define AVDB_LOFUPD_COUNT_NOT_ANNOTATED 3
+#define AVDB_LOFUPD_COUNT_BAD 4
+#define AVDB_LOFUPD_COUNT_OUT_BYTES 5
+#define AVDB_LOFUPD_COUNT_LONE_CR 6
+#define AVDB_LOFUPD_N_COUNTS 7
+typedef struct avdb_lof_table {
+  uint32_t struct_size; /* sizeof(avdb_lof_table) */
+  uint32_t reserved;
+  uint64_t n_rows;
+  const uint8_t* keys;     /* the rows' keys, in reverse row order */
+  const uint64_t* key_off; /* n_rows + 1 */
+  const void* keyset;      /* avdb_keyset_build over them */
+  uint64_t keyset_bytes;
+  const uint8_t* json;
+  uint64_t json_bytes;
+  const uint64_t* json_off; /* per row */
+  const uint32_t* json_len;
+  uint8_t* hit;             /* per row; NULL: not recorded */
+} avdb_lof_table;
+int avdb_lof_table_workspace_size(size_t text_bytes, size_t n_lines, size_t* bytes);
+int avdb_lof_table_size(avdb_ctx* ctx, const uint8_t* text, size_t text_bytes, size_t n_lines, uint64_t* ent_start,
+                        uint32_t* ent_alts, uint32_t* ent_key_bytes, uint32_t* ent_json_len, uint8_t* ent_flags,
+                        uint64_t* counts, void* workspace, size_t workspace_bytes, void* stream);
+int avdb_lof_table_write(avdb_ctx* ctx, const uint8_t* text, size_t text_bytes, size_t n_lines, size_t n_entries,
+                         size_t n_rows, const uint64_t* ent_start, const uint32_t* ent_alts,
+                         const uint32_t* ent_key_bytes, const uint32_t* ent_json_len, const uint8_t* ent_flags,
+                         uint8_t* keys, size_t key_cap, uint64_t* key_off, uint8_t* json, size_t json_cap,
+                         uint64_t* row_json_off, uint32_t* row_json_len, uint64_t* row_line_start, uint8_t* row_flags,
+                         uint64_t* totals, void* workspace, size_t workspace_bytes, void* stream);
+int avdb_lof_table_size_host(const avdb_ctx* ctx, const uint8_t* text, size_t text_bytes, size_t n_lines,
+                             uint64_t* ent_start, uint32_t* ent_alts, uint32_t* ent_key_bytes, uint32_t* ent_json_len,
+                             uint8_t* ent_flags, uint64_t* counts);
+int avdb_lof_table_write_host(const avdb_ctx* ctx, const uint8_t* text, size_t text_bytes, size_t n_lines,
+                              size_t n_entries, size_t n_rows, const uint64_t* ent_start, const uint32_t* ent_alts,
+                              const uint32_t* ent_key_bytes, const uint32_t* ent_json_len, const uint8_t* ent_flags,
+                              uint8_t* keys, size_t key_cap, uint64_t* key_off, uint8_t* json, size_t json_cap,
+                              uint64_t* row_json_off, uint32_t* row_json_len, uint64_t* row_line_start,
+                              uint8_t* row_flags, uint64_t* totals);
+int avdb_lof_update_workspace_size(size_t text_bytes, size_t n_lines, size_t* bytes);
+int avdb_lof_update_size(avdb_ctx* ctx, const uint8_t* text, size_t text_bytes, size_t n_lines,
+                         const avdb_lof_table* table, uint32_t contig_mask, uint32_t flags, uint64_t* row_start,
+                         uint32_t* pk_len, int32_t* match, uint32_t* out_len, uint8_t* row_flags, uint64_t* counts,
+                         void* workspace, size_t workspace_bytes, void* stream);
+int avdb_lof_update_write(avdb_ctx* ctx, const uint8_t* text, size_t text_bytes, size_t n_lines, size_t n_rows,
+                          const avdb_lof_table* table, const uint64_t* row_start, const uint32_t* pk_len,
+                          const int32_t* match, const uint32_t* out_len, const uint8_t* row_flags, uint8_t* out,
+                          size_t out_cap, uint64_t* row_off, uint64_t* totals, void* workspace, size_t workspace_bytes,
+                          void* stream);
+int avdb_lof_update_size_host(const avdb_ctx* ctx, const uint8_t* text, size_t text_bytes, size_t n_lines,
+                              const avdb_lof_table* table, uint32_t contig_mask, uint32_t flags, uint64_t* row_start,
+                              uint32_t* pk_len, int32_t* match, uint32_t* out_len, uint8_t* row_flags,
+                              uint64_t* counts);
+int avdb_lof_update_write_host(const avdb_ctx* ctx, const uint8_t* text, size_t text_bytes, size_t n_lines,
+                               size_t n_rows, const avdb_lof_table* table, const uint64_t* row_start,
+                               const uint32_t* pk_len, const int32_t* match, const uint32_t* out_len,
+                               const uint8_t* row_flags, uint8_t* out, size_t out_cap, uint64_t* row_off,
+                               uint64_t* totals);
 
 /* ---- host-side formatting of kernel outputs -------------------------------
  * ltree path text (<= AVDB_MAX_PATH bytes).  Returns the length written (no
