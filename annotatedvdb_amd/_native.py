@@ -84,6 +84,16 @@ LOFUPD_UPDATE_EXISTING = 1
 LOFUPD_COUNTS = ("rows", "skipped_lines", "skipped", "not_annotated", "bad", "out_bytes",
                  "lone_cr")  # AVDB_LOFUPD_COUNT_*, by slot
 LOFUPD_N_COUNTS = len(LOFUPD_COUNTS)
+QC_LINE_HOST, QC_LINE_BAD, QC_ROW_FIRST, QC_PASS = 1, 2, 4, 8  # AVDB_QC_* entry and row flags
+QC_RELEASE_MAX = 64
+QC_COUNTS = ("rows", "lines", "comment_lines", "host_lines", "bad", "key_bytes", "json_bytes", "lone_cr", "entries",
+             "pass")  # AVDB_QC_COUNT_*, by slot
+QC_N_COUNTS = len(QC_COUNTS)
+QCUPD_ROW_HOST, QCUPD_BAD = 1, 2  # AVDB_QCUPD_* row flags
+QCUPD_UPDATE_EXISTING = 1
+QCUPD_COUNTS = ("rows", "skipped_lines", "skipped", "not_in_vcf", "bad", "out_bytes", "lone_cr",
+                "host_rows")  # AVDB_QCUPD_COUNT_*, by slot
+QCUPD_N_COUNTS = len(QCUPD_COUNTS)
 EXPVCF_ROW_HOST, EXPVCF_BAD, EXPVCF_DROPPED = 1, 2, 4  # AVDB_EXPVCF_* row flags
 EXPVCF_STREAM_VCF, EXPVCF_STREAM_INVALID = 0, 1
 EXPVCF_COUNTS = ("valid", "invalid", "skipped_lines", "filtered", "bad", "lone_cr", "vcf_bytes",
@@ -145,6 +155,21 @@ class LofTableView(ctypes.Structure):
                          json_off, json_len, hit)
 
 
+class QcTableView(ctypes.Structure):
+    """avdb_qc_table (include/avdb.h); ``struct_size`` is filled in.  ``release`` is kept alive here."""
+    _fields_ = [("struct_size", ctypes.c_uint32), ("release_len", ctypes.c_uint32), ("n_rows", ctypes.c_uint64),
+                ("keys", ctypes.c_void_p), ("key_off", ctypes.c_void_p), ("keyset", ctypes.c_void_p),
+                ("keyset_bytes", ctypes.c_uint64), ("json", ctypes.c_void_p), ("json_bytes", ctypes.c_uint64),
+                ("json_off", ctypes.c_void_p), ("json_len", ctypes.c_void_p), ("flags", ctypes.c_void_p),
+                ("hit", ctypes.c_void_p), ("release", ctypes.c_char_p)]
+
+    def __init__(self, release: bytes = b"", n_rows: int = 0, keys=None, key_off=None, keyset=None,
+                 keyset_bytes: int = 0, json=None, json_bytes: int = 0, json_off=None, json_len=None, flags=None,
+                 hit=None):
+        super().__init__(ctypes.sizeof(QcTableView), len(release), n_rows, keys, key_off, keyset, keyset_bytes, json,
+                         json_bytes, json_off, json_len, flags, hit, release)
+
+
 class LineResult(ctypes.Structure):
     """avdb_line_result (include/avdb.h)."""
     _fields_ = [(name, ctypes.c_uint32) for name in ("state", "flags", "copy_bytes", "map_bytes", "n_rec", "n_rows",
@@ -191,6 +216,10 @@ EXPORTED_SYMBOLS = [
     "avdb_lof_table_size_host", "avdb_lof_table_write_host",
     "avdb_lof_update_workspace_size", "avdb_lof_update_size", "avdb_lof_update_write",
     "avdb_lof_update_size_host", "avdb_lof_update_write_host",
+    "avdb_qc_table_workspace_size", "avdb_qc_table_size", "avdb_qc_table_write",
+    "avdb_qc_table_size_host", "avdb_qc_table_write_host",
+    "avdb_qc_update_workspace_size", "avdb_qc_update_size", "avdb_qc_update_write",
+    "avdb_qc_update_size_host", "avdb_qc_update_write_host",
 ]
 
 
@@ -356,6 +385,18 @@ def _sig(lib):
     f.avdb_lof_update_size.argtypes = f.avdb_lof_update_size_host.argtypes + [P, SZ, P]
     f.avdb_lof_update_write_host.argtypes = [P, P, SZ, SZ, SZ, LT, P, P, P, P, P, P, SZ, P, P]
     f.avdb_lof_update_write.argtypes = f.avdb_lof_update_write_host.argtypes + [P, SZ, P]
+    QT = ctypes.POINTER(QcTableView)
+    f.avdb_qc_table_workspace_size.argtypes = [SZ, SZ, ctypes.POINTER(SZ)]
+    f.avdb_qc_table_size_host.argtypes = [P, P, SZ, SZ, ctypes.c_char_p, SZ] + [P] * 6
+    f.avdb_qc_table_size.argtypes = f.avdb_qc_table_size_host.argtypes + [P, SZ, P]
+    f.avdb_qc_table_write_host.argtypes = [P, P, SZ, SZ, SZ, SZ, ctypes.c_char_p, SZ, P, P, P, P, P, P, SZ, P, P, SZ,
+                                           P, P, P, P, P]
+    f.avdb_qc_table_write.argtypes = f.avdb_qc_table_write_host.argtypes + [P, SZ, P]
+    f.avdb_qc_update_workspace_size.argtypes = [SZ, SZ, ctypes.POINTER(SZ)]
+    f.avdb_qc_update_size_host.argtypes = [P, P, SZ, SZ, QT, U32, U32, P, P, P, P, P, P]
+    f.avdb_qc_update_size.argtypes = f.avdb_qc_update_size_host.argtypes + [P, SZ, P]
+    f.avdb_qc_update_write_host.argtypes = [P, P, SZ, SZ, SZ, QT, P, P, P, P, P, P, SZ, P, P]
+    f.avdb_qc_update_write.argtypes = f.avdb_qc_update_write_host.argtypes + [P, SZ, P]
     for name in EXPORTED_SYMBOLS:
         if name not in ("avdb_last_error",):
             getattr(f, name).restype = I32

@@ -182,6 +182,38 @@ class LofUpdateRows:
     counts: Dict[str, int]
 
 
+@dataclass
+class QcTable(LofTable):
+    """What K17a makes of an ADSP QC pVCF (:meth:`Engine.qc_table_build`): :class:`LofTable`'s
+    members for one row per ALT allele of every line, ``json`` holding each line's
+    ``json.dumps({release: {"info": ..., "filter": ..., "qual": ..., "format": ...}})``;
+    ``flags`` the rows' ``N.QC_*`` flags (``N.QC_PASS``: FILTER is ``PASS``); ``release`` the
+    release key's bytes; ``counts`` by ``N.QC_COUNTS``."""
+    release: bytes = b""
+
+    def view(self) -> "N.QcTableView":
+        if self.n_rows == 0:
+            return N.QcTableView(self.release)
+        return N.QcTableView(self.release, self.n_rows, N.ptr(self.rkeys), N.ptr(self.rkey_off), N.ptr(self.keyset),
+                             self.keyset.numel(), N.ptr(self.json), self.json.numel(), N.ptr(self.json_off),
+                             N.ptr(self.json_len), N.ptr(self.flags), N.ptr(self.hit))
+
+
+@dataclass
+class QcUpdateRows:
+    """What K17b makes of an export of ``AnnotatedVDB.Variant`` (:meth:`Engine.qc_update_rows`):
+    ``text`` holds the update rows (``pk<TAB>chr<label><TAB>true|\\N<TAB>json<LF>``, row ``i`` at
+    ``row_off[i] .. row_off[i + 1]``; a row the host found to have QC values already has no
+    bytes), ``n`` the rows with bytes, ``match`` the table row each was rendered from, ``flags``
+    their ``N.QCUPD_*`` flags, ``counts`` the pass's counts by name (``N.QCUPD_COUNTS``)."""
+    n: int
+    text: torch.Tensor
+    row_off: torch.Tensor
+    match: torch.Tensor
+    flags: torch.Tensor
+    counts: Dict[str, int]
+
+
 VCF_EXPORT_HEADER = b"#CHRM\tPOS\tID\tREF\tALT\tQUAL\tFILTER\tINFO\n"  # (sic) export_variant2vcf.py:26
 
 
@@ -1584,6 +1616,39 @@ class Engine:
         the line count, the size pass's counts, the end.  On a host-only engine the library's
         host entries run the same per-line code."""
         return slab_passes.lof_update_rows(self, text, table, update_existing, contigs)
+
+    # -- K17: ADSP QC pVCF update rows --------------------------------------------------
+    def qc_table_build(self, text, version: str, header_fields=None) -> "QcTable":
+        """K17a: a '\\n'-separated slab of an ADSP QC pVCF (bytes, numpy ``uint8`` or a ``uint8``
+        tensor) -> :class:`QcTable` on this engine's device.  A line is read as
+        ``load_annotation`` (``update_from_qc_pvcf_file.py:226-258``) reads it: ``rstrip()``ped;
+        ``#`` lines are comments; every other line gives one row per ALT allele, keyed
+        ``chrom:pos:ref:alt`` as in :meth:`lof_table_build`, one JSON text
+        ``{release: {"info": {...}, "filter": ..., "qual": ..., "format": ...}}`` as
+        ``generate_update_values`` (``:117-149``) builds it, ``release`` being
+        ``version.lower()``, and whether FILTER is ``PASS``.  Of an id the VCF repeats the last
+        record answers a probe.  Lines outside the device subset (``host_lines``: DESIGN.md, K17)
+        are rendered by :func:`annotatedvdb_amd.adsp_qc.qc_line` and copied into their spans
+        after the write pass; an exception it raises is re-raised with the line number attached
+        (``err.line``, 1-based, and a note).  ``header_fields`` other than the reference's
+        default nine leave every line to the host.  A release that is not 1 to 64 printable
+        ASCII bytes without ``"`` and ``\\`` raises ``ValueError``, as does a carriage return
+        inside a line.  Three syncs, as :meth:`lof_table_build`; on a host-only engine the
+        library's host entries run the same per-line code."""
+        return slab_passes.qc_table_build(self, text, version, header_fields)
+
+    def qc_update_rows(self, text, table: "QcTable", update_existing: bool = False, contigs=None) -> "QcUpdateRows":
+        """K17b: a slab of an export ``record_primary_key<TAB>metaseq_id<TAB>adsp_qc[<TAB>...]``
+        (K13's conventions, as :meth:`lof_update_rows`) streamed against a :class:`QcTable` ->
+        :class:`QcUpdateRows`: for every export row whose metaseq id the QC file holds the tuple
+        ``__buffer_update_values`` appends as ``pk<TAB>chr<label><TAB>true|\\N<TAB>json<LF>``, in
+        export order.  An id the table does not hold is counted ``not_in_vcf``; a record that
+        has QC values of this release already — its third column is not NULL and a key at depth
+        1 of its JSON object equals the release — is counted ``skipped`` and gets no row unless
+        ``update_existing``.  A column with a backslash in it, or that does not begin with
+        ``{``, is settled here with ``json.loads`` (``host_rows``); one that is not JSON raises
+        ``ValueError`` naming the export line.  ``table.hit`` records the table rows matched."""
+        return slab_passes.qc_update_rows(self, text, table, update_existing, contigs)
 
     # -- K14: the VCF files of an export ------------------------------------------
     def export_vcf(self, text, contigs=None, variants_per_file: int = 10_000_000) -> "ExportVcf":

@@ -1,6 +1,7 @@
 """The passes over a '\\n'-separated text slab behind :class:`~annotatedvdb_amd.engine.Engine`:
 K10a ``cadd_table_build``, K12 ``existing_table_build``, K13 ``cadd_update_rows``, K14
-``export_vcf``, K15 ``split_vcf`` and K16 ``lof_table_build`` / ``lof_update_rows``.
+``export_vcf``, K15 ``split_vcf``, K16 ``lof_table_build`` / ``lof_update_rows`` and K17
+``qc_table_build`` / ``qc_update_rows``.
 
 The two-pass ones have one shape: line count -> size pass -> its counts to the host (second
 sync) -> the rows the device leaves to the host rendered here -> outputs allocated -> write
@@ -382,37 +383,44 @@ def _line_number(sp: SlabPass, offset: int) -> int:
     return int((sp.text[:offset] == 10).sum()) + 1
 
 
-def lof_table_build(engine, text):
-    from .snpeff_lof import annotated_line
-    sp = SlabPass(engine, text, "lof_table", "avdb_lof_table_workspace_size")
+def _alt_table_build(engine, text, name: str, count_names, extra, host_line, all_host: bool = False):
+    """The table build K16a and K17a share: entry ``avdb_<name>_size`` / ``_write`` with ``extra``
+    arguments behind the line (and row) counts, one row per ALT allele of every entry, one JSON text
+    per entry.  ``host_line(line bytes, cnt)`` renders a line the device leaves to the host (flag 1 of
+    its entry): ``(lookup ids, JSON, row flag bits)``.  ``all_host``: every entry is such a line.
+    Returns :class:`~annotatedvdb_amd.engine.LofTable`'s members, in its order."""
+    sp = SlabPass(engine, text, name, f"avdb_{name}_workspace_size")
     ent_start, ent_alts, ent_key, ent_json, ent_flags = sp.cols(torch.int64, torch.int32, torch.int32, torch.int32,
                                                                 torch.uint8)
     ents = (ent_start, ent_alts, ent_key, ent_json, ent_flags)
-    counts = engine.empty(N.LOF_N_COUNTS, torch.int64)
-    sp.call("avdb_lof_table_size", sp.tp, sp.nb, sp.n_lines, *ents, counts)
-    cnt = sp.counts(counts, N.LOF_COUNTS)
+    counts = engine.empty(len(count_names), torch.int64)
+    sp.call(f"avdb_{name}_size", sp.tp, sp.nb, sp.n_lines, *extra, *ents, counts)
+    cnt = sp.counts(counts, count_names)
     if cnt["lone_cr"]:
         raise ValueError(f"{cnt['lone_cr']} carriage return(s) inside lines of the VCF: Python's text mode ends a "
                          "line there and the device pass does not")
     ne = cnt["entries"]
+    if all_host and ne:
+        ent_flags[:ne] |= 1
+        for col in (ent_alts, ent_key, ent_json):
+            col[:ne] = 0
+        cnt.update(rows=0, key_bytes=0, json_bytes=0, host_lines=ne)
     host = None
     if cnt["host_lines"]:
         # the lines outside the device subset: their text to the host, rendered in file order
-        host = torch.nonzero(ent_flags[:ne] & N.LOF_LINE_HOST).flatten()
-        host_keys, host_json = [], []
+        host = torch.nonzero(ent_flags[:ne] & 1).flatten()
+        host_keys, host_json, host_bits = [], [], []
         for at, b in zip(ent_start[host].tolist(), sp.rows_bytes(ent_start[host], _lines_to_next(sp, host, ent_start, ne))):
             try:
-                keys, js = annotated_line(b.split(b"\n", 1)[0])
+                keys, js, bits = host_line(b.split(b"\n", 1)[0], cnt)
             except Exception as err:
                 err.line = _line_number(sp, at)
                 if hasattr(err, "add_note"):
                     err.add_note(f"line {err.line} of the VCF")
                 raise
-            if not js:  # neither value: the line contributes nothing
-                keys = []
-                cnt["no_values"] += 1
             host_keys.append(keys)
             host_json.append(js)
+            host_bits.append(bits)
         alts = [len(k) for k in host_keys]
         kb = [sum(map(len, k)) for k in host_keys]
         cnt["rows"] += sum(alts)
@@ -429,7 +437,7 @@ def lof_table_build(engine, text):
     json_len = engine.empty(max(1, n), torch.int32)
     flags = engine.empty(max(1, n), torch.uint8)
     totals = engine.empty(4, torch.int64)
-    sp.call("avdb_lof_table_write", sp.tp, sp.nb, sp.n_lines, ne, n, *ents, keys, key_bytes, key_off, json_blob,
+    sp.call(f"avdb_{name}_write", sp.tp, sp.nb, sp.n_lines, ne, n, *extra, *ents, keys, key_bytes, key_off, json_blob,
             json_bytes, json_off, json_len, line_start, flags, totals)
     if host is not None and host.numel():
         def starts(lengths):  # where each entry's share of a blob (or its rows) begins
@@ -437,18 +445,21 @@ def lof_table_build(engine, text):
         koff, joff, roff = (starts(x)[host] for x in (ent_key, ent_json, ent_alts))
         sp.splice(keys, koff, [b"".join(k) for k in host_keys])
         sp.splice(json_blob, joff, host_json)
-        rows_at, offs = [], []
-        for first, base, ks in zip(roff.tolist(), koff.tolist(), host_keys):
+        rows_at, offs, bits_at = [], [], []
+        for first, base, ks, bits in zip(roff.tolist(), koff.tolist(), host_keys, host_bits):
             for a, k in enumerate(ks):
                 rows_at.append(first + a)
                 offs.append(base)
+                bits_at.append(bits)
                 base += len(k)
         if rows_at:
-            key_off[torch.tensor(rows_at, dtype=torch.int64).to(engine.device)] = \
-                torch.tensor(offs, dtype=torch.int64).to(engine.device)
+            at = torch.tensor(rows_at, dtype=torch.int64).to(engine.device)
+            key_off[at] = torch.tensor(offs, dtype=torch.int64).to(engine.device)
+            if any(bits_at):
+                flags[at] |= torch.tensor(bits_at, dtype=torch.uint8).to(engine.device)
     got = totals.cpu().tolist()
     if got[3] or got[:3] != [key_bytes, json_bytes, n]:
-        raise N.NativeError("avdb_lof_table_write" + sp.suffix, N.AVDB_ERANGE,
+        raise N.NativeError(f"avdb_{name}_write" + sp.suffix, N.AVDB_ERANGE,
                             f"totals {got[:3]} do not fit the sizes the size pass gave")
     # K6 keeps the first of equal keys: over the keys in reverse row order that is the last record of an id
     lens = (key_off[1:] - key_off[:-1]).flip(0)
@@ -456,8 +467,115 @@ def lof_table_build(engine, text):
     rkeys = keys[engine._spans(key_off[:-1].flip(0), lens)] if n else keys[:0]
     keyset = engine.keyset_table(rkeys, rkey_off)
     hit = torch.zeros(max(1, n), dtype=torch.uint8, device=engine.device)
-    return E.LofTable(engine, sp.text, n, keys[:key_bytes], key_off, rkeys, rkey_off, keyset, json_blob[:json_bytes],
-                      json_off[:n], json_len[:n], line_start[:n], flags[:n], hit[:n] if n else hit[:0], cnt)
+    return (engine, sp.text, n, keys[:key_bytes], key_off, rkeys, rkey_off, keyset, json_blob[:json_bytes],
+            json_off[:n], json_len[:n], line_start[:n], flags[:n], hit[:n] if n else hit[:0], cnt)
+
+
+def lof_table_build(engine, text):
+    from .snpeff_lof import annotated_line
+
+    def host_line(line, cnt):
+        keys, js = annotated_line(line)
+        if not js:  # neither value: the line contributes nothing
+            keys = []
+            cnt["no_values"] += 1
+        return keys, js, 0
+
+    return E.LofTable(*_alt_table_build(engine, text, "lof_table", N.LOF_COUNTS, (), host_line))
+
+
+def qc_release(version) -> bytes:
+    """The release key of a ``--version``: lower-cased, as ``get_datasource`` gives it
+    (``variant_loader.py:98``); the bytes the device writes and compares."""
+    release = str(version).lower().encode("utf-8")
+    if not 0 < len(release) <= N.QC_RELEASE_MAX or any(c < 0x20 or c > 0x7E or c in b'"\\' for c in release):
+        raise ValueError(f"version {version!r}: 1 to {N.QC_RELEASE_MAX} printable ASCII characters without "
+                         "'\"' and '\\' are taken")
+    return release
+
+
+def qc_table_build(engine, text, version, header_fields=None):
+    from .adsp_qc import HEADER_FIELDS, qc_line
+    release = qc_release(version)
+    fields = None if header_fields is None else list(header_fields)
+    plain = fields is None or [f.lower().replace("#", "") for f in fields] == \
+        [f.lower().replace("#", "") for f in HEADER_FIELDS]
+
+    def host_line(line, cnt):
+        keys, js, passed = qc_line(line, release.decode("ascii"), fields)
+        cnt["pass"] += passed
+        return keys, js, N.QC_PASS if passed else 0
+
+    # (a release that holds "Infinity" makes generate_update_values raise for every line: the host's too)
+    parts = _alt_table_build(engine, text, "qc_table", N.QC_COUNTS, (release, len(release)), host_line,
+                             not plain or b"Infinity" in release)
+    return E.QcTable(*parts, release)
+
+
+def _copy_text(column: bytes) -> str:
+    """A column of ``COPY ... TO``'s text format without its backslash escapes."""
+    out, i, n = bytearray(), 0, len(column)
+    esc = {0x62: 8, 0x66: 12, 0x6E: 10, 0x72: 13, 0x74: 9, 0x76: 11}
+    while i < n:
+        c = column[i]
+        if c == 0x5C and i + 1 < n:
+            i += 1
+            c = esc.get(column[i], column[i])
+        out.append(c)
+        i += 1
+    return out.decode("utf-8")
+
+
+def qc_update_rows(engine, text, table, update_existing: bool = False, contigs=None):
+    import json
+    if table.text.device != engine.device:
+        raise ValueError("QC table lives on another device than this engine")
+    view = table.view()
+    vp = ctypes.byref(view)
+    sp = SlabPass(engine, text, "qc_update", "avdb_qc_update_workspace_size")
+    row_start, pk_len, match, out_len, flags = sp.cols(torch.int64, torch.int32, torch.int32, torch.int32, torch.uint8)
+    counts = engine.empty(N.QCUPD_N_COUNTS, torch.int64)
+    sp.call("avdb_qc_update_size", sp.tp, sp.nb, sp.n_lines, vp, E.existing_contig_mask(contigs),
+            N.QCUPD_UPDATE_EXISTING if update_existing else 0, row_start, pk_len, match, out_len, flags, counts)
+    cnt = sp.counts(counts, N.QCUPD_COUNTS)
+    if cnt["lone_cr"]:
+        sp.raise_lone_cr(cnt["lone_cr"], "pass does not")
+    n = cnt["rows"]
+    if cnt["bad"]:
+        sp.raise_bad_metaseq(row_start, flags, N.QCUPD_BAD, n, cnt["bad"])
+    out_bytes = cnt["out_bytes"]
+    dropped = 0
+    if cnt["host_rows"]:
+        # the columns the device does not scan: json.loads and Python's `in`, as load():49 has it
+        host_rows = torch.nonzero(flags[:n] & N.QCUPD_ROW_HOST).flatten()
+        release = table.release.decode("ascii")
+        drop = []
+        for r, at, b in zip(host_rows.tolist(), row_start[host_rows].tolist(),
+                            sp.rows_bytes(row_start[host_rows], _lines_to_next(sp, host_rows, row_start, n))):
+            line = b.split(b"\n", 1)[0]
+            column = (line[:-1] if line.endswith(b"\r") and len(line) < len(b) else line).split(b"\t")[2]
+            try:
+                value = json.loads(_copy_text(column))
+            except ValueError as err:
+                bad = ValueError(f"line {_line_number(sp, at)} of the export: the adsp_qc column is not JSON ({err})")
+                bad.line = _line_number(sp, at)
+                raise bad from err
+            if value is not None and release in value:
+                drop.append(r)
+        if drop:
+            drop_t = torch.tensor(drop, dtype=torch.int64, device=engine.device)
+            out_bytes -= int(out_len[drop_t].sum())
+            out_len[drop_t] = 0
+            dropped = len(drop)
+            cnt["skipped"] += dropped
+    cnt["out_bytes"] = out_bytes
+    out_text = engine.empty(max(1, out_bytes), torch.uint8)
+    row_off = engine.empty(n + 1, torch.int64)
+    totals = engine.empty(2, torch.int64)
+    sp.call("avdb_qc_update_write", sp.tp, sp.nb, sp.n_lines, n, vp, row_start, pk_len, match, out_len, flags,
+            out_text, out_bytes, row_off, totals)
+    sp.check_totals("avdb_qc_update_write", totals.cpu().tolist(), out_bytes, "rows")
+    return E.QcUpdateRows(n - dropped, out_text[:out_bytes], row_off, match[:n], flags[:n], cnt)
 
 
 def lof_update_rows(engine, text, table, update_existing: bool = False, contigs=None):

@@ -1323,6 +1323,115 @@ int avdb_lof_update_write_host(const avdb_ctx* ctx, const uint8_t* text, size_t 
                                const uint8_t* row_flags, uint8_t* out, size_t out_cap, uint64_t* row_off,
                                uint64_t* totals);
 
+/* ---- K17: ADSP QC pVCF update rows (Load/bin/update_from_qc_pvcf_file.py) ----
+ * K17a, the table: `text` is a '\n'-separated slab of an ADSP QC pVCF.  A line is read as
+ * load_annotation reads it (:226-258): rstrip()ped; a '#' line is a comment; every other line
+ * is an entry, read by the header #CHROM .. FORMAT (nine fields; columns beyond the ninth are
+ * ignored).  An entry yields one table row per ALT allele, the lookup id chrom:pos:ref:alt as
+ * the row's key (as K16a), and one JSON text shared by the line's rows,
+ *   json.dumps({release: {"info": {...}, "filter": v, "qual": v, "format": v}})
+ * with INFO as parse_entry splits it (a bare flag is true, '#' reads ':') and every value as
+ * to_numeric leaves it.  `release` (1 .. AVDB_QC_RELEASE_MAX bytes, none of them '"', '\',
+ * a control byte or above 0x7F) is written as it is.  AVDB_QC_PASS marks an entry whose FILTER
+ * is exactly PASS.  An entry outside the device subset is flagged
+ * AVDB_QC_LINE_HOST and treated as K16a treats its host lines; AVDB_QC_LINE_BAD marks the host
+ * lines with fewer than nine fields.
+ *   1. avdb_qc_table_size, 2. avdb_qc_table_write: the arrays, totals and alignment of
+ *      avdb_lof_table_size / avdb_lof_table_write; row_flags hold AVDB_QC_ROW_FIRST,
+ *      AVDB_QC_LINE_HOST and AVDB_QC_PASS.
+ * K17b, the update rows: `text` is a slab of an export
+ * record_primary_key<TAB>metaseq_id<TAB>adsp_qc[<TAB>...] read by K13's conventions.  The id
+ * is probed as in K16b: no hit counts NOT_IN_VCF; a hit on row t stores 1 to table->hit[t] and
+ * is the row pk<TAB>chr<label><TAB>true|\N<TAB>json of t<LF> (true: row t has AVDB_QC_PASS),
+ * unless, without AVDB_QCUPD_UPDATE_EXISTING, the third field is not NULL (absent, empty, \N)
+ * and a key at depth 1 of its JSON object equals the release (counted SKIPPED, no row).  A third
+ * field that holds a '\' or does not begin with '{' makes the row AVDB_QCUPD_ROW_HOST: it is
+ * sized and written as an update row and the caller settles whether it is one.
+ * avdb_qc_table: avdb_lof_table's members, the rows' flags and the release. */
+#define AVDB_QC_LINE_HOST 0x01u
+#define AVDB_QC_LINE_BAD 0x02u
+#define AVDB_QC_ROW_FIRST 0x04u
+#define AVDB_QC_PASS 0x08u
+#define AVDB_QC_RELEASE_MAX 64
+#define AVDB_QC_COUNT_ROWS 0
+#define AVDB_QC_COUNT_LINES 1
+#define AVDB_QC_COUNT_COMMENT_LINES 2
+#define AVDB_QC_COUNT_HOST_LINES 3
+#define AVDB_QC_COUNT_BAD 4
+#define AVDB_QC_COUNT_KEY_BYTES 5
+#define AVDB_QC_COUNT_JSON_BYTES 6
+#define AVDB_QC_COUNT_LONE_CR 7
+#define AVDB_QC_COUNT_ENTRIES 8
+#define AVDB_QC_COUNT_PASS 9
+#define AVDB_QC_N_COUNTS 10
+#define AVDB_QCUPD_ROW_HOST 0x01u
+#define AVDB_QCUPD_BAD 0x02u
+#define AVDB_QCUPD_UPDATE_EXISTING 0x01u /* avdb_qc_update_size's flags */
+#define AVDB_QCUPD_COUNT_ROWS 0
+#define AVDB_QCUPD_COUNT_SKIPPED_LINES 1
+#define AVDB_QCUPD_COUNT_SKIPPED 2
+#define AVDB_QCUPD_COUNT_NOT_IN_VCF 3
+#define AVDB_QCUPD_COUNT_BAD 4
+#define AVDB_QCUPD_COUNT_OUT_BYTES 5
+#define AVDB_QCUPD_COUNT_LONE_CR 6
+#define AVDB_QCUPD_COUNT_HOST_ROWS 7
+#define AVDB_QCUPD_N_COUNTS 8
+typedef struct avdb_qc_table {
+  uint32_t struct_size; /* sizeof(avdb_qc_table) */
+  uint32_t release_len;
+  uint64_t n_rows;
+  const uint8_t* keys;     /* the rows' keys, in reverse row order */
+  const uint64_t* key_off; /* n_rows + 1 */
+  const void* keyset;      /* avdb_keyset_build over them */
+  uint64_t keyset_bytes;
+  const uint8_t* json;
+  uint64_t json_bytes;
+  const uint64_t* json_off; /* per row */
+  const uint32_t* json_len;
+  const uint8_t* flags;     /* per row: AVDB_QC_PASS */
+  uint8_t* hit;             /* per row; NULL: not recorded */
+  const uint8_t* release;   /* host memory, release_len bytes */
+} avdb_qc_table;
+int avdb_qc_table_workspace_size(size_t text_bytes, size_t n_lines, size_t* bytes);
+int avdb_qc_table_size(avdb_ctx* ctx, const uint8_t* text, size_t text_bytes, size_t n_lines, const uint8_t* release,
+                       size_t release_len, uint64_t* ent_start, uint32_t* ent_alts, uint32_t* ent_key_bytes,
+                       uint32_t* ent_json_len, uint8_t* ent_flags, uint64_t* counts, void* workspace,
+                       size_t workspace_bytes, void* stream);
+int avdb_qc_table_write(avdb_ctx* ctx, const uint8_t* text, size_t text_bytes, size_t n_lines, size_t n_entries,
+                        size_t n_rows, const uint8_t* release, size_t release_len, const uint64_t* ent_start,
+                        const uint32_t* ent_alts, const uint32_t* ent_key_bytes, const uint32_t* ent_json_len,
+                        const uint8_t* ent_flags, uint8_t* keys, size_t key_cap, uint64_t* key_off, uint8_t* json,
+                        size_t json_cap, uint64_t* row_json_off, uint32_t* row_json_len, uint64_t* row_line_start,
+                        uint8_t* row_flags, uint64_t* totals, void* workspace, size_t workspace_bytes, void* stream);
+int avdb_qc_table_size_host(const avdb_ctx* ctx, const uint8_t* text, size_t text_bytes, size_t n_lines,
+                            const uint8_t* release, size_t release_len, uint64_t* ent_start, uint32_t* ent_alts,
+                            uint32_t* ent_key_bytes, uint32_t* ent_json_len, uint8_t* ent_flags, uint64_t* counts);
+int avdb_qc_table_write_host(const avdb_ctx* ctx, const uint8_t* text, size_t text_bytes, size_t n_lines,
+                             size_t n_entries, size_t n_rows, const uint8_t* release, size_t release_len,
+                             const uint64_t* ent_start, const uint32_t* ent_alts, const uint32_t* ent_key_bytes,
+                             const uint32_t* ent_json_len, const uint8_t* ent_flags, uint8_t* keys, size_t key_cap,
+                             uint64_t* key_off, uint8_t* json, size_t json_cap, uint64_t* row_json_off,
+                             uint32_t* row_json_len, uint64_t* row_line_start, uint8_t* row_flags, uint64_t* totals);
+int avdb_qc_update_workspace_size(size_t text_bytes, size_t n_lines, size_t* bytes);
+int avdb_qc_update_size(avdb_ctx* ctx, const uint8_t* text, size_t text_bytes, size_t n_lines,
+                        const avdb_qc_table* table, uint32_t contig_mask, uint32_t flags, uint64_t* row_start,
+                        uint32_t* pk_len, int32_t* match, uint32_t* out_len, uint8_t* row_flags, uint64_t* counts,
+                        void* workspace, size_t workspace_bytes, void* stream);
+int avdb_qc_update_write(avdb_ctx* ctx, const uint8_t* text, size_t text_bytes, size_t n_lines, size_t n_rows,
+                         const avdb_qc_table* table, const uint64_t* row_start, const uint32_t* pk_len,
+                         const int32_t* match, const uint32_t* out_len, const uint8_t* row_flags, uint8_t* out,
+                         size_t out_cap, uint64_t* row_off, uint64_t* totals, void* workspace, size_t workspace_bytes,
+                         void* stream);
+int avdb_qc_update_size_host(const avdb_ctx* ctx, const uint8_t* text, size_t text_bytes, size_t n_lines,
+                             const avdb_qc_table* table, uint32_t contig_mask, uint32_t flags, uint64_t* row_start,
+                             uint32_t* pk_len, int32_t* match, uint32_t* out_len, uint8_t* row_flags,
+                             uint64_t* counts);
+int avdb_qc_update_write_host(const avdb_ctx* ctx, const uint8_t* text, size_t text_bytes, size_t n_lines,
+                              size_t n_rows, const avdb_qc_table* table, const uint64_t* row_start,
+                              const uint32_t* pk_len, const int32_t* match, const uint32_t* out_len,
+                              const uint8_t* row_flags, uint8_t* out, size_t out_cap, uint64_t* row_off,
+                              uint64_t* totals);
+
 /* ---- host-side formatting of kernel outputs -------------------------------
  * ltree path text (<= AVDB_MAX_PATH bytes).  Returns the length written (no
  * NUL terminator counted; one is written if cap allows), or a negative code. */
