@@ -94,6 +94,19 @@ QCUPD_UPDATE_EXISTING = 1
 QCUPD_COUNTS = ("rows", "skipped_lines", "skipped", "not_in_vcf", "bad", "out_bytes", "lone_cr",
                 "host_rows")  # AVDB_QCUPD_COUNT_*, by slot
 QCUPD_N_COUNTS = len(QCUPD_COUNTS)
+TXT_MAX_FIELDS = 32
+TXT_LINE_HOST, TXT_LINE_BAD, TXT_ROW_PK_CHROM = 1, 2, 4  # AVDB_TXT_* entry and row flags
+TXT_ADSP = 1  # the update and direct entries' flags
+TXT_COUNTS = ("rows", "lines", "skipped_lines", "host_lines", "bad", "key_bytes", "json_bytes", "lone_cr",
+              "entries")  # AVDB_TXT_COUNT_*, by slot
+TXT_N_COUNTS = len(TXT_COUNTS)
+TXTUPD_TABLE_HOST, TXTUPD_BAD = 1, 2  # AVDB_TXTUPD_* row flags
+TXTUPD_COUNTS = ("rows", "skipped_lines", "not_in_file", "bad", "out_bytes", "lone_cr",
+                 "host_rows")  # AVDB_TXTUPD_COUNT_*, by slot
+TXTUPD_N_COUNTS = len(TXTUPD_COUNTS)
+TXTDIR_COUNTS = ("rows", "lines", "skipped_lines", "host_rows", "bad", "out_bytes",
+                 "lone_cr")  # AVDB_TXTDIR_COUNT_*, by slot
+TXTDIR_N_COUNTS = len(TXTDIR_COUNTS)
 EXPVCF_ROW_HOST, EXPVCF_BAD, EXPVCF_DROPPED = 1, 2, 4  # AVDB_EXPVCF_* row flags
 EXPVCF_STREAM_VCF, EXPVCF_STREAM_INVALID = 0, 1
 EXPVCF_COUNTS = ("valid", "invalid", "skipped_lines", "filtered", "bad", "lone_cr", "vcf_bytes",
@@ -170,6 +183,20 @@ class QcTableView(ctypes.Structure):
                          json_bytes, json_off, json_len, flags, hit, release)
 
 
+class TxtTableView(ctypes.Structure):
+    """avdb_txt_table (include/avdb.h); ``struct_size`` is filled in."""
+    _fields_ = [("struct_size", ctypes.c_uint32), ("reserved", ctypes.c_uint32), ("n_rows", ctypes.c_uint64),
+                ("keys", ctypes.c_void_p), ("key_off", ctypes.c_void_p), ("keyset", ctypes.c_void_p),
+                ("keyset_bytes", ctypes.c_uint64), ("body", ctypes.c_void_p), ("body_bytes", ctypes.c_uint64),
+                ("body_off", ctypes.c_void_p), ("body_len", ctypes.c_void_p), ("flags", ctypes.c_void_p),
+                ("hit", ctypes.c_void_p)]
+
+    def __init__(self, n_rows: int = 0, keys=None, key_off=None, keyset=None, keyset_bytes: int = 0, body=None,
+                 body_bytes: int = 0, body_off=None, body_len=None, flags=None, hit=None):
+        super().__init__(ctypes.sizeof(TxtTableView), 0, n_rows, keys, key_off, keyset, keyset_bytes, body, body_bytes,
+                         body_off, body_len, flags, hit)
+
+
 class LineResult(ctypes.Structure):
     """avdb_line_result (include/avdb.h)."""
     _fields_ = [(name, ctypes.c_uint32) for name in ("state", "flags", "copy_bytes", "map_bytes", "n_rec", "n_rows",
@@ -220,6 +247,12 @@ EXPORTED_SYMBOLS = [
     "avdb_qc_table_size_host", "avdb_qc_table_write_host",
     "avdb_qc_update_workspace_size", "avdb_qc_update_size", "avdb_qc_update_write",
     "avdb_qc_update_size_host", "avdb_qc_update_write_host",
+    "avdb_txt_table_workspace_size", "avdb_txt_table_size", "avdb_txt_table_write",
+    "avdb_txt_table_size_host", "avdb_txt_table_write_host",
+    "avdb_txt_update_workspace_size", "avdb_txt_update_size", "avdb_txt_update_write",
+    "avdb_txt_update_size_host", "avdb_txt_update_write_host",
+    "avdb_txt_direct_workspace_size", "avdb_txt_direct_size", "avdb_txt_direct_write",
+    "avdb_txt_direct_size_host", "avdb_txt_direct_write_host",
 ]
 
 
@@ -397,6 +430,23 @@ def _sig(lib):
     f.avdb_qc_update_size.argtypes = f.avdb_qc_update_size_host.argtypes + [P, SZ, P]
     f.avdb_qc_update_write_host.argtypes = [P, P, SZ, SZ, SZ, QT, P, P, P, P, P, P, SZ, P, P]
     f.avdb_qc_update_write.argtypes = f.avdb_qc_update_write_host.argtypes + [P, SZ, P]
+    TT = ctypes.POINTER(TxtTableView)
+    f.avdb_txt_table_workspace_size.argtypes = [SZ, SZ, ctypes.POINTER(SZ)]
+    f.avdb_txt_table_size_host.argtypes = [P, P, SZ, SZ, U32, U32, U32, U32] + [P] * 6
+    f.avdb_txt_table_size.argtypes = f.avdb_txt_table_size_host.argtypes + [P, SZ, P]
+    f.avdb_txt_table_write_host.argtypes = [P, P, SZ, SZ, SZ, SZ, U32, U32, U32, U32, P, P, P, P, P, P, SZ, P, P, SZ,
+                                            P, P, P, P, P]
+    f.avdb_txt_table_write.argtypes = f.avdb_txt_table_write_host.argtypes + [P, SZ, P]
+    f.avdb_txt_update_workspace_size.argtypes = [SZ, SZ, ctypes.POINTER(SZ)]
+    f.avdb_txt_update_size_host.argtypes = [P, P, SZ, SZ, TT, U32, U32, U32, P, P, P, P, P, P]
+    f.avdb_txt_update_size.argtypes = f.avdb_txt_update_size_host.argtypes + [P, SZ, P]
+    f.avdb_txt_update_write_host.argtypes = [P, P, SZ, SZ, SZ, TT, U32, P, P, P, P, P, P, SZ, P, P]
+    f.avdb_txt_update_write.argtypes = f.avdb_txt_update_write_host.argtypes + [P, SZ, P]
+    f.avdb_txt_direct_workspace_size.argtypes = [SZ, SZ, ctypes.POINTER(SZ)]
+    f.avdb_txt_direct_size_host.argtypes = [P, P, SZ, SZ, U32, U32, U32, U32, P, P, P, P]
+    f.avdb_txt_direct_size.argtypes = f.avdb_txt_direct_size_host.argtypes + [P, SZ, P]
+    f.avdb_txt_direct_write_host.argtypes = [P, P, SZ, SZ, SZ, U32, U32, U32, U32, P, P, P, P, SZ, P, P]
+    f.avdb_txt_direct_write.argtypes = f.avdb_txt_direct_write_host.argtypes + [P, SZ, P]
     for name in EXPORTED_SYMBOLS:
         if name not in ("avdb_last_error",):
             getattr(f, name).restype = I32

@@ -118,15 +118,18 @@ inline int host_row_offsets(const char* fn, const uint32_t* out_len, size_t n_ro
 // caller's kStageBytes of LDS (s_out) is rendered to global memory bytewise.
 // load(r) gives row r's columns, read once, before the trip's staged-or-not branch;
 // render(row, put) renders them through put(k, c): byte k of the row is c, k below the
-// row's out_len (row_off[r + 1] - row_off[r]).
-template <uint32_t kStageBytes, class Load, class Render>
+// row's out_len (row_off[r + 1] - row_off[r]).  begin_trip(r0, nr) runs in every thread of the
+// workgroup before rows [r0, r0 + nr) are loaded (K19 stages their lines' text there); what it
+// leaves in LDS may be read until the trip's rows are rendered.
+template <uint32_t kStageBytes, class BeginTrip, class Load, class Render>
 __device__ __forceinline__ void write_rows(const uint64_t* __restrict__ row_off, size_t n_rows,
                                            uint8_t* __restrict__ out, const uint64_t* __restrict__ totals,
-                                           uint64_t* s_out, Load load, Render render) {
+                                           uint64_t* s_out, BeginTrip begin_trip, Load load, Render render) {
   if (totals[1]) return;  // the capacity is too small: nothing is written
   uint8_t* s_bytes = reinterpret_cast<uint8_t*>(s_out);
   for (size_t r0 = size_t(blockIdx.x) * kBlock; r0 < n_rows; r0 += size_t(gridDim.x) * kBlock) {
     const uint32_t nr = n_rows - r0 < kBlock ? uint32_t(n_rows - r0) : uint32_t(kBlock);
+    begin_trip(r0, nr);
     const uint64_t b = row_off[r0], e = row_off[r0 + nr], b8 = b & ~7ull;
     const bool staged = e >= b && e - b8 <= kStageBytes;  // (workgroup-uniform)
     const uint32_t t = threadIdx.x;
@@ -156,6 +159,13 @@ __device__ __forceinline__ void write_rows(const uint64_t* __restrict__ row_off,
     }
     __syncthreads();  // the stage is reused by the next trip
   }
+}
+
+template <uint32_t kStageBytes, class Load, class Render>
+__device__ __forceinline__ void write_rows(const uint64_t* __restrict__ row_off, size_t n_rows,
+                                           uint8_t* __restrict__ out, const uint64_t* __restrict__ totals,
+                                           uint64_t* s_out, Load load, Render render) {
+  write_rows<kStageBytes>(row_off, n_rows, out, totals, s_out, [](size_t, uint32_t) {}, load, render);
 }
 
 }  // namespace rows

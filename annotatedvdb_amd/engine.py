@@ -214,6 +214,51 @@ class QcUpdateRows:
     counts: Dict[str, int]
 
 
+@dataclass
+class TxtHeader:
+    """The header of a tab-delimited annotation file as ``csv`` reads it
+    (:func:`annotatedvdb_amd.text_update.read_header`): ``fields`` its names, ``skip_lines`` the
+    slab's lines up to and including it, ``id_col`` the column named ``variant``, ``key_col`` the
+    column that is looked up (``id_col``; the ``ref_snp_id`` column for refSNP ids)."""
+    fields: List[str]
+    skip_lines: int
+    id_col: int
+    key_col: int
+
+    def extra(self):
+        return (self.skip_lines, len(self.fields), self.id_col, self.key_col)
+
+
+@dataclass
+class TxtTable(LofTable):
+    """What K19a makes of a tab-delimited annotation file (:meth:`Engine.txt_table_build`):
+    :class:`LofTable`'s members for one row per data line, keyed by the looked-up id; ``json``
+    holds each row's body ``<label><TAB><update values>`` (the label is the id up to its first
+    ``:``; ``N.TXT_ROW_PK_CHROM`` in ``flags`` marks an id without one, whose chromosome comes from
+    the primary key); ``header`` the :class:`TxtHeader`; ``counts`` by ``N.TXT_COUNTS``."""
+    header: Optional[TxtHeader] = None
+
+    def view(self) -> "N.TxtTableView":
+        if self.n_rows == 0:
+            return N.TxtTableView()
+        return N.TxtTableView(self.n_rows, N.ptr(self.rkeys), N.ptr(self.rkey_off), N.ptr(self.keyset),
+                              self.keyset.numel(), N.ptr(self.json), self.json.numel(), N.ptr(self.json_off),
+                              N.ptr(self.json_len), N.ptr(self.flags), N.ptr(self.hit))
+
+
+@dataclass
+class TxtUpdateRows:
+    """What K19b and K19c make (:meth:`Engine.txt_update_rows`, :meth:`Engine.txt_direct_rows`):
+    ``text`` holds the ``n`` update rows (``pk<TAB>chr<label><TAB>values[<TAB>true]<LF>``, row ``i``
+    at ``row_off[i] .. row_off[i + 1]``), ``match`` the table row each was rendered from (``None``
+    for K19c), ``counts`` the pass's counts by name (``N.TXTUPD_COUNTS`` / ``N.TXTDIR_COUNTS``)."""
+    n: int
+    text: torch.Tensor
+    row_off: torch.Tensor
+    match: Optional[torch.Tensor]
+    counts: Dict[str, int]
+
+
 VCF_EXPORT_HEADER = b"#CHRM\tPOS\tID\tREF\tALT\tQUAL\tFILTER\tINFO\n"  # (sic) export_variant2vcf.py:26
 
 
@@ -1649,6 +1694,45 @@ class Engine:
         ``{``, is settled here with ``json.loads`` (``host_rows``); one that is not JSON raises
         ``ValueError`` naming the export line.  ``table.hit`` records the table rows matched."""
         return slab_passes.qc_update_rows(self, text, table, update_existing, contigs)
+
+    # -- K19: annotation update rows from a tab-delimited file --------------------------
+    def txt_table_build(self, text, variant_id_type: str = "METASEQ") -> "TxtTable":
+        """K19a: a '\\n'-separated slab of a tab-delimited file with a header (bytes, numpy
+        ``uint8`` or a ``uint8`` tensor) -> :class:`TxtTable` on this engine's device.  The header
+        is read on the host by ``csv`` from the slab's first bytes (one small copy); it must name a
+        column ``variant`` and at least one, at most ``N.TXT_MAX_FIELDS - 1`` others, and for
+        ``variant_id_type='REFSNP'`` a column ``ref_snp_id``, which is then the looked-up one
+        (``set_current_variant``, ``txt_variant_loader.py:177-178``), else ``ValueError``.  A data
+        line gives one row: its looked-up id as key and its update values, every header column but
+        ``variant`` in header order, rendered once (``NULL`` and the fields a short row lacks as
+        ``\\N``, fields beyond the header dropped, empty lines skipped).  Of an id the file
+        repeats the last line answers a probe.  Lines outside the device subset (``host_lines``: a
+        field that starts with ``"``, a byte above 0x7F, a field that is exactly ``\\N``) are
+        rendered by :func:`annotatedvdb_amd.text_update.host_line` and copied into their spans
+        after the write pass; an exception it raises carries the line number (``err.line``).  A
+        carriage return inside a line raises ``ValueError``.  Three syncs and the header's copy;
+        on a host-only engine the library's host entries run the same per-line code."""
+        return slab_passes.txt_table_build(self, text, variant_id_type)
+
+    def txt_update_rows(self, text, table: "TxtTable", id_type: str = "METASEQ", adsp: bool = False,
+                        contigs=None) -> "TxtUpdateRows":
+        """K19b: a slab of an export ``record_primary_key<TAB>metaseq_id<TAB>ref_snp_id[<TAB>...]``
+        (K13's conventions, as :meth:`lof_update_rows`; the third column ``\\N``, empty or absent
+        for none) streamed against a :class:`TxtTable` -> :class:`TxtUpdateRows`: for every export
+        row whose id (``id_type``: ``METASEQ`` the second column, ``REFSNP`` the third) the file
+        holds, the tuple ``__buffer_update_values`` appends (``txt_variant_loader.py:190-208``) as
+        ``pk<TAB>chr<label><TAB>values[<TAB>true]<LF>`` (``true`` with ``adsp``), in export order;
+        several primary keys of one id all get a row.  An id the table does not hold is counted
+        ``not_in_file``.  ``table.hit`` records the table rows matched."""
+        return slab_passes.txt_update_rows(self, text, table, id_type, adsp, contigs)
+
+    def txt_direct_rows(self, text, adsp: bool = False) -> "TxtUpdateRows":
+        """K19c: a slab of a tab-delimited file whose ``variant`` column holds primary keys ->
+        :class:`TxtUpdateRows`, one row per data line in file order (the reference asks the
+        database nothing for such a file).  The header, the update values and the host lines are
+        :meth:`txt_table_build`'s; a host line's row is rendered by
+        :func:`annotatedvdb_amd.text_update.host_line` and copied into its span."""
+        return slab_passes.txt_direct_rows(self, text, adsp)
 
     # -- K14: the VCF files of an export ------------------------------------------
     def export_vcf(self, text, contigs=None, variants_per_file: int = 10_000_000) -> "ExportVcf":

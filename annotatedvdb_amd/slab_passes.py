@@ -1,7 +1,8 @@
 """The passes over a '\\n'-separated text slab behind :class:`~annotatedvdb_amd.engine.Engine`:
 K10a ``cadd_table_build``, K12 ``existing_table_build``, K13 ``cadd_update_rows``, K14
-``export_vcf``, K15 ``split_vcf``, K16 ``lof_table_build`` / ``lof_update_rows`` and K17
-``qc_table_build`` / ``qc_update_rows``.
+``export_vcf``, K15 ``split_vcf``, K16 ``lof_table_build`` / ``lof_update_rows``, K17
+``qc_table_build`` / ``qc_update_rows`` and K19 ``txt_table_build`` / ``txt_update_rows`` /
+``txt_direct_rows``.
 
 The two-pass ones have one shape: line count -> size pass -> its counts to the host (second
 sync) -> the rows the device leaves to the host rendered here -> outputs allocated -> write
@@ -383,10 +384,11 @@ def _line_number(sp: SlabPass, offset: int) -> int:
     return int((sp.text[:offset] == 10).sum()) + 1
 
 
-def _alt_table_build(engine, text, name: str, count_names, extra, host_line, all_host: bool = False):
-    """The table build K16a and K17a share: entry ``avdb_<name>_size`` / ``_write`` with ``extra``
-    arguments behind the line (and row) counts, one row per ALT allele of every entry, one JSON text
-    per entry.  ``host_line(line bytes, cnt)`` renders a line the device leaves to the host (flag 1 of
+def _alt_table_build(engine, text, name: str, count_names, extra, host_line, all_host: bool = False,
+                     what: str = "VCF"):
+    """The table build K16a, K17a and K19a share: entry ``avdb_<name>_size`` / ``_write`` with ``extra``
+    arguments behind the line (and row) counts, one row per ALT allele of every entry (K19a: one row
+    per entry), one JSON text (K19a: body) per entry; ``what`` names the file in messages.  ``host_line(line bytes, cnt)`` renders a line the device leaves to the host (flag 1 of
     its entry): ``(lookup ids, JSON, row flag bits)``.  ``all_host``: every entry is such a line.
     Returns :class:`~annotatedvdb_amd.engine.LofTable`'s members, in its order."""
     sp = SlabPass(engine, text, name, f"avdb_{name}_workspace_size")
@@ -397,7 +399,7 @@ def _alt_table_build(engine, text, name: str, count_names, extra, host_line, all
     sp.call(f"avdb_{name}_size", sp.tp, sp.nb, sp.n_lines, *extra, *ents, counts)
     cnt = sp.counts(counts, count_names)
     if cnt["lone_cr"]:
-        raise ValueError(f"{cnt['lone_cr']} carriage return(s) inside lines of the VCF: Python's text mode ends a "
+        raise ValueError(f"{cnt['lone_cr']} carriage return(s) inside lines of the {what}: Python's text mode ends a "
                          "line there and the device pass does not")
     ne = cnt["entries"]
     if all_host and ne:
@@ -416,7 +418,7 @@ def _alt_table_build(engine, text, name: str, count_names, extra, host_line, all
             except Exception as err:
                 err.line = _line_number(sp, at)
                 if hasattr(err, "add_note"):
-                    err.add_note(f"line {err.line} of the VCF")
+                    err.add_note(f"line {err.line} of the {what}")
                 raise
             host_keys.append(keys)
             host_json.append(js)
@@ -602,3 +604,94 @@ def lof_update_rows(engine, text, table, update_existing: bool = False, contigs=
             out_text, out_bytes, row_off, totals)
     sp.check_totals("avdb_lof_update_write", totals.cpu().tolist(), out_bytes, "rows")
     return E.LofUpdateRows(n, out_text[:out_bytes], row_off, match[:n], cnt)
+
+
+def _txt_header(engine, text, variant_id_type: str):
+    """The slab as a tensor and its header, read by ``csv`` from the first bytes (one small copy)."""
+    from .text_update import HEADER_WINDOW, read_header
+    text = engine._as_text(text)
+    return text, read_header(text[:HEADER_WINDOW].cpu().numpy().tobytes(), variant_id_type, text.numel())
+
+
+def txt_table_build(engine, text, variant_id_type: str = "METASEQ"):
+    from .text_update import host_line as render
+    text, header = _txt_header(engine, text, variant_id_type)
+
+    def host_line(line, cnt):
+        key, label, tail = render(line, header)
+        return [key], (label or b"") + b"\t" + tail, 0 if label is not None else N.TXT_ROW_PK_CHROM
+
+    parts = _alt_table_build(engine, text, "txt_table", N.TXT_COUNTS, header.extra(), host_line, what="file")
+    return E.TxtTable(*parts, header)
+
+
+def txt_update_rows(engine, text, table, id_type: str = "METASEQ", adsp: bool = False, contigs=None):
+    if id_type not in ("METASEQ", "REFSNP"):
+        raise ValueError("id_type must be 'METASEQ' or 'REFSNP' (a file of primary keys needs no export: "
+                         "txt_direct_rows)")
+    if table.text.device != engine.device:
+        raise ValueError("the table lives on another device than this engine")
+    view = table.view()
+    vp = ctypes.byref(view)
+    key_col, flags_arg = (1 if id_type == "METASEQ" else 2), (N.TXT_ADSP if adsp else 0)
+    sp = SlabPass(engine, text, "txt_update", "avdb_txt_update_workspace_size")
+    row_start, pk_len, match, out_len, flags = sp.cols(torch.int64, torch.int32, torch.int32, torch.int32, torch.uint8)
+    counts = engine.empty(N.TXTUPD_N_COUNTS, torch.int64)
+    sp.call("avdb_txt_update_size", sp.tp, sp.nb, sp.n_lines, vp, E.existing_contig_mask(contigs), key_col, flags_arg,
+            row_start, pk_len, match, out_len, flags, counts)
+    cnt = sp.counts(counts, N.TXTUPD_COUNTS)
+    if cnt["lone_cr"]:
+        sp.raise_lone_cr(cnt["lone_cr"], "pass does not")
+    n = cnt["rows"]
+    if cnt["bad"]:
+        sp.raise_bad_metaseq(row_start, flags, N.TXTUPD_BAD, n, cnt["bad"])
+    out_bytes = cnt["out_bytes"]
+    out_text = engine.empty(max(1, out_bytes), torch.uint8)
+    row_off = engine.empty(n + 1, torch.int64)
+    totals = engine.empty(2, torch.int64)
+    sp.call("avdb_txt_update_write", sp.tp, sp.nb, sp.n_lines, n, vp, flags_arg, row_start, pk_len, match, out_len,
+            flags, out_text, out_bytes, row_off, totals)
+    sp.check_totals("avdb_txt_update_write", totals.cpu().tolist(), out_bytes, "rows")
+    return E.TxtUpdateRows(n, out_text[:out_bytes], row_off, match[:n], cnt)
+
+
+def txt_direct_rows(engine, text, adsp: bool = False):
+    from .text_update import host_line as render
+    text, header = _txt_header(engine, text, "PRIMARY_KEY")
+    shape = (header.skip_lines, len(header.fields), header.id_col, N.TXT_ADSP if adsp else 0)
+    sp = SlabPass(engine, text, "txt_direct", "avdb_txt_direct_workspace_size")
+    row_start, out_len, flags = sp.cols(torch.int64, torch.int32, torch.uint8)
+    counts = engine.empty(N.TXTDIR_N_COUNTS, torch.int64)
+    sp.call("avdb_txt_direct_size", sp.tp, sp.nb, sp.n_lines, *shape, row_start, out_len, flags, counts)
+    cnt = sp.counts(counts, N.TXTDIR_COUNTS)
+    if cnt["lone_cr"]:
+        raise ValueError(f"{cnt['lone_cr']} carriage return(s) inside lines of the file: Python's text mode ends a "
+                         "line there and the device pass does not")
+    n, out_bytes = cnt["rows"], cnt["out_bytes"]
+    host_rows = rendered = None
+    if cnt["host_rows"]:
+        host_rows = torch.nonzero(flags[:n] & N.TXT_LINE_HOST).flatten()
+        rendered = []
+        for at, b in zip(row_start[host_rows].tolist(),
+                         sp.rows_bytes(row_start[host_rows], _lines_to_next(sp, host_rows, row_start, n))):
+            try:
+                pk, label, tail = render(b.split(b"\n", 1)[0], header)
+            except Exception as err:
+                err.line = _line_number(sp, at)
+                if hasattr(err, "add_note"):
+                    err.add_note(f"line {err.line} of the file")
+                raise
+            chrom = label if label is not None else pk.split(b":")[0]
+            rendered.append(pk + b"\tchr" + chrom + b"\t" + tail + (b"\ttrue" if adsp else b"") + b"\n")
+        out_bytes += sum(map(len, rendered))
+        out_len[host_rows] = sp.lengths(rendered).to(torch.int32)
+    cnt["out_bytes"] = out_bytes
+    out_text = engine.empty(max(1, out_bytes), torch.uint8)
+    row_off = engine.empty(n + 1, torch.int64)
+    totals = engine.empty(2, torch.int64)
+    sp.call("avdb_txt_direct_write", sp.tp, sp.nb, sp.n_lines, n, *shape, row_start, out_len, flags, out_text,
+            out_bytes, row_off, totals)
+    if rendered is not None:
+        sp.splice(out_text, row_off[host_rows], rendered)
+    sp.check_totals("avdb_txt_direct_write", totals.cpu().tolist(), out_bytes, "rows")
+    return E.TxtUpdateRows(n, out_text[:out_bytes], row_off, None, cnt)

@@ -1432,6 +1432,145 @@ int avdb_qc_update_write_host(const avdb_ctx* ctx, const uint8_t* text, size_t t
                               const uint8_t* row_flags, uint8_t* out, size_t out_cap, uint64_t* row_off,
                               uint64_t* totals);
 
+/* ---- K19: annotation update rows from a tab-delimited file (Load/bin/update_variant_annotation.py) ----
+ * `text` is a '\n'-separated slab of a tab-delimited file with a header.  The header is the
+ * caller's (csv's own parse): skip_lines is the number of the slab's lines up to and including
+ * it, n_fields (2 .. AVDB_TXT_MAX_FIELDS) its field count, id_col the field named `variant`,
+ * key_col the field that is looked up (id_col, or the `ref_snp_id` column for refSNP ids).  A
+ * line behind the header is a data line unless it is empty ("\r\n" ends a line too; a '\r'
+ * elsewhere is counted LONE_CR).  Its update values ("tail") are its first n_fields fields
+ * without field id_col, joined by tabs: a field that is exactly NULL, and a field a short line
+ * lacks, reads \N; fields beyond n_fields are dropped.  Its chromosome is chr<label>, the label
+ * being the id up to its first ':', or, for an id without one, the primary key up to its first
+ * ':'.  A data line outside the device subset is flagged AVDB_TXT_LINE_HOST and left to the
+ * caller: a field that starts with '"', a byte above 0x7F, a field that is exactly \N;
+ * AVDB_TXT_LINE_BAD as well for a line that lacks field id_col or key_col or whose looked-up
+ * field is empty.
+ * K19a, the table (one row per data line, the arrays, totals and alignment of
+ * avdb_lof_table_size / avdb_lof_table_write; ent_alts is 1, or 0 for a host line until the
+ * caller patches it): the row's key is its looked-up field, its body <label><TAB><tail>, the
+ * label left out and AVDB_TXT_ROW_PK_CHROM set when the id has no ':'.
+ * K19b, the update rows: `text` is a slab of an export
+ * record_primary_key<TAB>metaseq_id<TAB>ref_snp_id[<TAB>...] read by K13's conventions (header
+ * line, fewer than two fields, contig mask by the metaseq id, a metaseq id without exactly three
+ * ':' is a row flagged AVDB_TXTUPD_BAD).  Field key_col (1: metaseq_id; 2: ref_snp_id, none
+ * when absent, empty or \N) is probed in the table's key set: no hit counts NOT_IN_FILE; a hit
+ * on row t stores 1 to table->hit[t] and is the row pk<TAB>chr<label><TAB><tail>[<TAB>true]<LF>
+ * (`true` with AVDB_TXT_ADSP in flags).  AVDB_TXTUPD_TABLE_HOST marks a row of a host-rendered
+ * table row.  avdb_txt_table: as avdb_lof_table, the keys in REVERSE row order, so the last line
+ * of a repeated id answers.
+ * K19c, a file whose `variant` column holds primary keys: every data line is the row
+ * pk<TAB>chr<label><TAB><tail>[<TAB>true]<LF>, in file order; a host line is a row of no bytes
+ * whose out_len the caller patches and whose span it fills.
+ * Workspaces: avdb_txt_*_workspace_size bytes, 256-byte aligned; outputs 8-byte aligned; the
+ * device entries enqueue on `stream`, the _host forms run the same per-line code on host arrays. */
+#define AVDB_TXT_MAX_FIELDS 32
+#define AVDB_TXT_LINE_HOST 0x01u
+#define AVDB_TXT_LINE_BAD 0x02u
+#define AVDB_TXT_ROW_PK_CHROM 0x04u
+#define AVDB_TXT_ADSP 0x01u /* the update and direct entries' flags */
+#define AVDB_TXT_COUNT_ROWS 0
+#define AVDB_TXT_COUNT_LINES 1
+#define AVDB_TXT_COUNT_SKIPPED_LINES 2
+#define AVDB_TXT_COUNT_HOST_LINES 3
+#define AVDB_TXT_COUNT_BAD 4
+#define AVDB_TXT_COUNT_KEY_BYTES 5
+#define AVDB_TXT_COUNT_JSON_BYTES 6 /* the bodies' bytes (the slot K16a and K17a name so) */
+#define AVDB_TXT_COUNT_LONE_CR 7
+#define AVDB_TXT_COUNT_ENTRIES 8
+#define AVDB_TXT_N_COUNTS 9
+#define AVDB_TXTUPD_TABLE_HOST 0x01u
+#define AVDB_TXTUPD_BAD 0x02u
+#define AVDB_TXTUPD_COUNT_ROWS 0
+#define AVDB_TXTUPD_COUNT_SKIPPED_LINES 1
+#define AVDB_TXTUPD_COUNT_NOT_IN_FILE 2
+#define AVDB_TXTUPD_COUNT_BAD 3
+#define AVDB_TXTUPD_COUNT_OUT_BYTES 4
+#define AVDB_TXTUPD_COUNT_LONE_CR 5
+#define AVDB_TXTUPD_COUNT_HOST_ROWS 6
+#define AVDB_TXTUPD_N_COUNTS 7
+#define AVDB_TXTDIR_COUNT_ROWS 0
+#define AVDB_TXTDIR_COUNT_LINES 1
+#define AVDB_TXTDIR_COUNT_SKIPPED_LINES 2
+#define AVDB_TXTDIR_COUNT_HOST_ROWS 3
+#define AVDB_TXTDIR_COUNT_BAD 4
+#define AVDB_TXTDIR_COUNT_OUT_BYTES 5
+#define AVDB_TXTDIR_COUNT_LONE_CR 6
+#define AVDB_TXTDIR_N_COUNTS 7
+typedef struct avdb_txt_table {
+  uint32_t struct_size; /* sizeof(avdb_txt_table) */
+  uint32_t reserved;
+  uint64_t n_rows;
+  const uint8_t* keys;     /* the rows' keys, in reverse row order */
+  const uint64_t* key_off; /* n_rows + 1 */
+  const void* keyset;      /* avdb_keyset_build over them */
+  uint64_t keyset_bytes;
+  const uint8_t* body;
+  uint64_t body_bytes;
+  const uint64_t* body_off; /* per row */
+  const uint32_t* body_len;
+  const uint8_t* flags;     /* per row: AVDB_TXT_ROW_PK_CHROM, AVDB_TXT_LINE_HOST */
+  uint8_t* hit;             /* per row; NULL: not recorded */
+} avdb_txt_table;
+int avdb_txt_table_workspace_size(size_t text_bytes, size_t n_lines, size_t* bytes);
+int avdb_txt_table_size(avdb_ctx* ctx, const uint8_t* text, size_t text_bytes, size_t n_lines, uint32_t skip_lines,
+                        uint32_t n_fields, uint32_t id_col, uint32_t key_col, uint64_t* ent_start, uint32_t* ent_alts,
+                        uint32_t* ent_key_bytes, uint32_t* ent_body_len, uint8_t* ent_flags, uint64_t* counts,
+                        void* workspace, size_t workspace_bytes, void* stream);
+int avdb_txt_table_write(avdb_ctx* ctx, const uint8_t* text, size_t text_bytes, size_t n_lines, size_t n_entries,
+                         size_t n_rows, uint32_t skip_lines, uint32_t n_fields, uint32_t id_col, uint32_t key_col,
+                         const uint64_t* ent_start, const uint32_t* ent_alts, const uint32_t* ent_key_bytes,
+                         const uint32_t* ent_body_len, const uint8_t* ent_flags, uint8_t* keys, size_t key_cap,
+                         uint64_t* key_off, uint8_t* body, size_t body_cap, uint64_t* row_body_off,
+                         uint32_t* row_body_len, uint64_t* row_line_start, uint8_t* row_flags, uint64_t* totals,
+                         void* workspace, size_t workspace_bytes, void* stream);
+int avdb_txt_table_size_host(const avdb_ctx* ctx, const uint8_t* text, size_t text_bytes, size_t n_lines,
+                             uint32_t skip_lines, uint32_t n_fields, uint32_t id_col, uint32_t key_col,
+                             uint64_t* ent_start, uint32_t* ent_alts, uint32_t* ent_key_bytes, uint32_t* ent_body_len,
+                             uint8_t* ent_flags, uint64_t* counts);
+int avdb_txt_table_write_host(const avdb_ctx* ctx, const uint8_t* text, size_t text_bytes, size_t n_lines,
+                              size_t n_entries, size_t n_rows, uint32_t skip_lines, uint32_t n_fields, uint32_t id_col,
+                              uint32_t key_col, const uint64_t* ent_start, const uint32_t* ent_alts,
+                              const uint32_t* ent_key_bytes, const uint32_t* ent_body_len, const uint8_t* ent_flags,
+                              uint8_t* keys, size_t key_cap, uint64_t* key_off, uint8_t* body, size_t body_cap,
+                              uint64_t* row_body_off, uint32_t* row_body_len, uint64_t* row_line_start,
+                              uint8_t* row_flags, uint64_t* totals);
+int avdb_txt_update_workspace_size(size_t text_bytes, size_t n_lines, size_t* bytes);
+int avdb_txt_update_size(avdb_ctx* ctx, const uint8_t* text, size_t text_bytes, size_t n_lines,
+                         const avdb_txt_table* table, uint32_t contig_mask, uint32_t key_col, uint32_t flags,
+                         uint64_t* row_start, uint32_t* pk_len, int32_t* match, uint32_t* out_len, uint8_t* row_flags,
+                         uint64_t* counts, void* workspace, size_t workspace_bytes, void* stream);
+int avdb_txt_update_write(avdb_ctx* ctx, const uint8_t* text, size_t text_bytes, size_t n_lines, size_t n_rows,
+                          const avdb_txt_table* table, uint32_t flags, const uint64_t* row_start,
+                          const uint32_t* pk_len, const int32_t* match, const uint32_t* out_len,
+                          const uint8_t* row_flags, uint8_t* out, size_t out_cap, uint64_t* row_off, uint64_t* totals,
+                          void* workspace, size_t workspace_bytes, void* stream);
+int avdb_txt_update_size_host(const avdb_ctx* ctx, const uint8_t* text, size_t text_bytes, size_t n_lines,
+                              const avdb_txt_table* table, uint32_t contig_mask, uint32_t key_col, uint32_t flags,
+                              uint64_t* row_start, uint32_t* pk_len, int32_t* match, uint32_t* out_len,
+                              uint8_t* row_flags, uint64_t* counts);
+int avdb_txt_update_write_host(const avdb_ctx* ctx, const uint8_t* text, size_t text_bytes, size_t n_lines,
+                               size_t n_rows, const avdb_txt_table* table, uint32_t flags, const uint64_t* row_start,
+                               const uint32_t* pk_len, const int32_t* match, const uint32_t* out_len,
+                               const uint8_t* row_flags, uint8_t* out, size_t out_cap, uint64_t* row_off,
+                               uint64_t* totals);
+int avdb_txt_direct_workspace_size(size_t text_bytes, size_t n_lines, size_t* bytes);
+int avdb_txt_direct_size(avdb_ctx* ctx, const uint8_t* text, size_t text_bytes, size_t n_lines, uint32_t skip_lines,
+                         uint32_t n_fields, uint32_t id_col, uint32_t flags, uint64_t* row_start, uint32_t* out_len,
+                         uint8_t* row_flags, uint64_t* counts, void* workspace, size_t workspace_bytes, void* stream);
+int avdb_txt_direct_write(avdb_ctx* ctx, const uint8_t* text, size_t text_bytes, size_t n_lines, size_t n_rows,
+                          uint32_t skip_lines, uint32_t n_fields, uint32_t id_col, uint32_t flags,
+                          const uint64_t* row_start, const uint32_t* out_len, const uint8_t* row_flags, uint8_t* out,
+                          size_t out_cap, uint64_t* row_off, uint64_t* totals, void* workspace, size_t workspace_bytes,
+                          void* stream);
+int avdb_txt_direct_size_host(const avdb_ctx* ctx, const uint8_t* text, size_t text_bytes, size_t n_lines,
+                              uint32_t skip_lines, uint32_t n_fields, uint32_t id_col, uint32_t flags,
+                              uint64_t* row_start, uint32_t* out_len, uint8_t* row_flags, uint64_t* counts);
+int avdb_txt_direct_write_host(const avdb_ctx* ctx, const uint8_t* text, size_t text_bytes, size_t n_lines,
+                               size_t n_rows, uint32_t skip_lines, uint32_t n_fields, uint32_t id_col, uint32_t flags,
+                               const uint64_t* row_start, const uint32_t* out_len, const uint8_t* row_flags,
+                               uint8_t* out, size_t out_cap, uint64_t* row_off, uint64_t* totals);
+
 /* ---- host-side formatting of kernel outputs -------------------------------
  * ltree path text (<= AVDB_MAX_PATH bytes).  Returns the length written (no
  * NUL terminator counted; one is written if cap allows), or a negative code. */
