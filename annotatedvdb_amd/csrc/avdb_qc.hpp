@@ -429,11 +429,7 @@ struct UpdLine {
   uint32_t lone_cr, coll;
 };
 
-struct UpdRow {
-  uint64_t start;
-  uint32_t pk_len, out_len, flags;
-  int32_t row;
-};
+using UpdRow = lof::UpdRow;
 
 enum ColumnQc : uint32_t { kNoQc = 0, kHasQc = 1, kAskHost = 2 };
 

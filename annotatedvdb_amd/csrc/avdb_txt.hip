@@ -2,33 +2,36 @@
 //
 // Replaces the per-line Python of Load/bin/update_variant_annotation.py on TextVariantLoader (a
 // csv.DictReader row dict, a split(':') and a SimpleNamespace, a database lookup of the id, a loop
-// over the update fields with its 'NULL' test, a tuple) with three device passes of two steps each.
+// over the update fields with its 'NULL' test, a tuple) with three device passes of two steps each,
+// K19a and K19b on the skeleton of avdb_tables.hpp as K16 is (avdb_lof.hip).
 // The header is the host's (csv's own parse of the slab's first bytes): the entries take the lines
 // to skip, the header's field count and the columns of `variant` and of the looked-up id.
-//   K19a, the table (avdb_txt_table_size / avdb_txt_table_write) over the file: K16a's shape
+//   K19a, the table (avdb_txt_table_size / avdb_txt_table_write) over the file
 //     k_txt_lines    one lane per line (lines::for_each_line): the line rule, the id, the length
 //                    of the update values; 16 bytes of info and a mark per line
-//     k_txt_compact  one lane per line: an entry's columns to its entry number; the counts
-//     (the write entry: three exclusive scans; k_txt_totals: the totals against the capacities)
+//     tables::k_compact<TxtBuild>, tables::k_totals
 //     k_txt_keys     rows::write_rows over the key blob, one lane per entry: its looked-up id
 //     k_txt_bodies   rows::write_rows over the body blob, one lane per entry: <label><TAB><values>
 //                    (both read a trip's lines from LDS, staged per trip as the size pass stages them)
-//   K19b, the update rows (avdb_txt_update_size / avdb_txt_update_write) over the export: K16b's
-//   shape with the looked-up column chosen by key_col
-//     k_txtupd_lines, k_txtupd_compact, rows::begin_write, k_txtupd_write
+//   K19b, the update rows (avdb_txt_update_size / avdb_txt_update_write) over the export, with
+//   the looked-up column chosen by key_col
+//     k_txtupd_lines, tables::k_upd_compact<TxtJoin>, rows::begin_write,
+//     tables::k_upd_write<kTxtWriteStage, TxtRows>
 //   K19c, the update rows of a file of primary keys (avdb_txt_direct_size / avdb_txt_direct_write)
 //     k_txtdir_lines, k_txtdir_compact, rows::begin_write, k_txtdir_write
 // The per-line and per-row code is avdb_txt.hpp, shared with the _host entries.
 #include "avdb_txt.hpp"
-#include "avdb_rows.hpp"
-
-#include <string.h>
+#include "avdb_tables.hpp"
 
 namespace avdb {
 
-using lof::EntryRow;
-using lof::RowCols;
-using lof::UpdRow;
+using tables::EntCols;
+using tables::EntryRow;
+using tables::EntScans;
+using tables::RowCols;
+using tables::UpdCols;
+using tables::UpdRow;
+using tables::upd_layout;
 using txt::Shape;
 
 // Lines of such a file are tens of bytes to a few hundred (a JSON value): a trip that does not
@@ -76,12 +79,30 @@ __device__ __forceinline__ void with_trip_line(const uint8_t* __restrict__ text,
                     [&](const uint8_t* line, uint64_t len, bool nl, bool have) { f((glb_cp)line, len, nl, have); });
 }
 
-struct TxtEntCols {  // per entry, n_lines entries allocated
-  uint64_t* start;
-  uint32_t* alts;
-  uint32_t* key_bytes;
-  uint32_t* body_len;
-  uint8_t* flags;
+struct TxtBuild {  // (JSON_BYTES: the bodies' bytes)
+  static constexpr int ROWS = AVDB_TXT_COUNT_ROWS, LINES = AVDB_TXT_COUNT_LINES, KEY_BYTES = AVDB_TXT_COUNT_KEY_BYTES,
+                       JSON_BYTES = AVDB_TXT_COUNT_JSON_BYTES, HOST_LINES = AVDB_TXT_COUNT_HOST_LINES,
+                       BAD = AVDB_TXT_COUNT_BAD, ENTRIES = AVDB_TXT_COUNT_ENTRIES, EXTRA = -1;
+  static constexpr uint32_t HOST_BIT = AVDB_TXT_LINE_HOST, BAD_BIT = AVDB_TXT_LINE_BAD, EXTRA_BIT = 0;
+  static constexpr bool ROW_PER_ENTRY = true;
+  static AVDB_HD bool is_entry(uint32_t w) { return (w & 1u) != 0; }
+};
+
+struct TxtJoin {  // (no record is skipped for what it holds already)
+  static constexpr int ROWS = AVDB_TXTUPD_COUNT_ROWS, SKIPPED_LINES = AVDB_TXTUPD_COUNT_SKIPPED_LINES, SKIPPED = -1,
+                       MISSED = AVDB_TXTUPD_COUNT_NOT_IN_FILE, BAD = AVDB_TXTUPD_COUNT_BAD,
+                       OUT_BYTES = AVDB_TXTUPD_COUNT_OUT_BYTES, LONE_CR = AVDB_TXTUPD_COUNT_LONE_CR,
+                       HOST_ROWS = AVDB_TXTUPD_COUNT_HOST_ROWS;
+  static constexpr uint32_t BAD_BIT = AVDB_TXTUPD_BAD, HOST_BIT = AVDB_TXTUPD_TABLE_HOST;
+};
+
+struct TxtRows {  // an update row against the table
+  txt::Table T;
+  uint32_t adsp;
+  template <class TextAt, class Put>
+  AVDB_HD void operator()(const UpdRow& row, TextAt text, Put put) const {
+    txt::render_update_row(row, T, adsp != 0, text, put);
+  }
 };
 
 // info[li] = {alts, key_bytes, body_len, is_entry | flags << 8}
@@ -107,74 +128,8 @@ __global__ __launch_bounds__(kBlock) void k_txt_lines(const uint8_t* __restrict_
   wave_add(&counts[AVDB_TXT_COUNT_SKIPPED_LINES], n_skip);
 }
 
-__global__ __launch_bounds__(kBlock) void k_txt_compact(const uint64_t* __restrict__ starts, size_t text_bytes,
-                                                        size_t n_lines, const u32x4* __restrict__ info,
-                                                        const uint64_t* __restrict__ ent_of, TxtEntCols o,
-                                                        unsigned long long* __restrict__ counts) {
-  uint64_t rows = 0, kb = 0, bb = 0;
-  uint32_t n_host = 0, n_bad = 0;
-  for (size_t li = size_t(blockIdx.x) * blockDim.x + threadIdx.x; li < n_lines; li += size_t(gridDim.x) * blockDim.x) {
-    const u32x4 v = info[li];
-    if (!(v.w & 1u)) continue;
-    const uint64_t e = ent_of[li];  // e < n_lines: at most one entry per line
-    uint64_t s = starts[li];
-    if (s > text_bytes) s = text_bytes;
-    const uint32_t flags = (v.w >> 8) & 0xFFu;
-    o.start[e] = s;
-    o.alts[e] = v.x;
-    o.key_bytes[e] = v.y;
-    o.body_len[e] = v.z;
-    o.flags[e] = uint8_t(flags);
-    rows += v.x;
-    kb += v.y;
-    bb += v.z;
-    n_host += (flags & AVDB_TXT_LINE_HOST) != 0;
-    n_bad += (flags & AVDB_TXT_LINE_BAD) != 0;
-  }
-  if (blockIdx.x == 0 && threadIdx.x == 0) {
-    counts[AVDB_TXT_COUNT_ENTRIES] = ent_of[n_lines];
-    counts[AVDB_TXT_COUNT_LINES] = n_lines;
-  }
-  wave_add(&counts[AVDB_TXT_COUNT_ROWS], rows);
-  wave_add(&counts[AVDB_TXT_COUNT_KEY_BYTES], kb);
-  wave_add(&counts[AVDB_TXT_COUNT_JSON_BYTES], bb);
-  wave_add(&counts[AVDB_TXT_COUNT_HOST_LINES], n_host);
-  wave_add(&counts[AVDB_TXT_COUNT_BAD], n_bad);
-}
-
-struct TxtEntScans {  // n_entries + 1 each
-  uint64_t* row;
-  uint64_t* key;
-  uint64_t* body;
-};
-
-// the three totals against the capacities; totals[3]: 1 when they do not fit (nothing is written)
-__global__ void k_txt_totals(TxtEntCols o, TxtEntScans sc, size_t n_entries, uint64_t n_rows, uint64_t key_cap,
-                             uint64_t body_cap, uint64_t* __restrict__ key_off, uint64_t* __restrict__ totals) {
-  if (blockIdx.x || threadIdx.x) return;
-  uint64_t r = 0, k = 0, j = 0;
-  if (n_entries) {
-    r = sc.row[n_entries - 1] + o.alts[n_entries - 1];
-    k = sc.key[n_entries - 1] + o.key_bytes[n_entries - 1];
-    j = sc.body[n_entries - 1] + o.body_len[n_entries - 1];
-  }
-  sc.row[n_entries] = r;
-  sc.key[n_entries] = k;
-  sc.body[n_entries] = j;
-  const bool over = k > key_cap || j > body_cap || r != n_rows;
-  totals[0] = k;
-  totals[1] = j;
-  totals[2] = r;
-  totals[3] = over;
-  if (!over) key_off[n_rows] = k;
-}
-
-__device__ __forceinline__ EntryRow txt_load_entry(const TxtEntCols& o, const TxtEntScans& sc, size_t e) {
-  return EntryRow{o.start[e], o.alts[e], o.key_bytes[e], o.body_len[e], o.flags[e], sc.row[e], sc.key[e], sc.body[e]};
-}
-
 __global__ __launch_bounds__(kBlock) void k_txt_keys(const uint8_t* __restrict__ text, size_t text_bytes, Shape S,
-                                                     TxtEntCols o, TxtEntScans sc, size_t n_entries, RowCols R,
+                                                     EntCols o, EntScans sc, size_t n_entries, RowCols R,
                                                      uint8_t* __restrict__ keys, const uint64_t* __restrict__ totals) {
   __shared__ uint64_t s_out[kTxtWriteStage / 8];
   __shared__ u32x4 s_text[kTxtWriteStage / 16];
@@ -183,7 +138,7 @@ __global__ __launch_bounds__(kBlock) void k_txt_keys(const uint8_t* __restrict__
   rows::write_rows<kTxtWriteStage>(
       sc.key, n_entries, keys, totals + 2, s_out,
       [&](size_t r0, uint32_t nr) { trip = stage_trip<kTxtWriteStage>(h, o.start, r0, nr, n_entries, text_bytes, s_text); },
-      [&](size_t e) { return txt_load_entry(o, sc, e); },
+      [&](size_t e) { return tables::load_entry(o, sc, e); },
       [&](const EntryRow& E, auto put) {
         with_trip_line(text, text_bytes, h, trip, s_text, E.start, [&](auto line, uint64_t len, bool nl, bool have) {
           txt::render_entry_key(line, len, nl, have, E, R, S, put);
@@ -192,7 +147,7 @@ __global__ __launch_bounds__(kBlock) void k_txt_keys(const uint8_t* __restrict__
 }
 
 __global__ __launch_bounds__(kBlock) void k_txt_bodies(const uint8_t* __restrict__ text, size_t text_bytes, Shape S,
-                                                       TxtEntCols o, TxtEntScans sc, size_t n_entries,
+                                                       EntCols o, EntScans sc, size_t n_entries,
                                                        uint8_t* __restrict__ body,
                                                        const uint64_t* __restrict__ totals) {
   __shared__ uint64_t s_out[kTxtWriteStage / 8];
@@ -200,9 +155,9 @@ __global__ __launch_bounds__(kBlock) void k_txt_bodies(const uint8_t* __restrict
   const Heap h = make_heap(text, text_bytes);
   TripText trip;
   rows::write_rows<kTxtWriteStage>(
-      sc.body, n_entries, body, totals + 2, s_out,
+      sc.json, n_entries, body, totals + 2, s_out,
       [&](size_t r0, uint32_t nr) { trip = stage_trip<kTxtWriteStage>(h, o.start, r0, nr, n_entries, text_bytes, s_text); },
-      [&](size_t e) { return txt_load_entry(o, sc, e); },
+      [&](size_t e) { return tables::load_entry(o, sc, e); },
       [&](const EntryRow& E, auto put) {
         with_trip_line(text, text_bytes, h, trip, s_text, E.start, [&](auto line, uint64_t len, bool nl, bool have) {
           txt::render_entry_body(line, len, nl, have, E, S, put);
@@ -211,15 +166,6 @@ __global__ __launch_bounds__(kBlock) void k_txt_bodies(const uint8_t* __restrict
 }
 
 // ---- K19b ---------------------------------------------------------------------------------
-struct TxtUpdCols {  // per row, n_lines entries allocated
-  uint64_t* row_start;
-  uint32_t* pk_len;
-  int32_t* match;
-  uint32_t* out_len;
-  uint8_t* flags;
-};
-
-// info[li] = {pk_len, out_len, match, flags | is_row << 8}
 __global__ __launch_bounds__(kBlock) void k_txtupd_lines(const uint8_t* __restrict__ text, size_t text_bytes,
                                                          const uint64_t* __restrict__ starts, size_t n_lines,
                                                          txt::Table T, uint32_t contig_mask, uint32_t key_col,
@@ -227,67 +173,14 @@ __global__ __launch_bounds__(kBlock) void k_txtupd_lines(const uint8_t* __restri
                                                          uint64_t* __restrict__ mark,
                                                          unsigned long long* __restrict__ counts) {
   __shared__ u32x4 s_text[kTxtUpdSizeStage / 16];
-  uint64_t n_cr = 0;
-  uint32_t n_miss = 0;
+  tables::UpdTally<TxtJoin> tally;
   lines::for_each_line<kTxtUpdSizeStage>(text, text_bytes, starts, n_lines, s_text, [&](size_t li, auto with_line) {
     with_line([&](uint64_t, uint64_t len, bool nl, auto line) {
       const txt::UpdLine L = txt::scan_export_line(line, len, nl, contig_mask, key_col, adsp != 0, T);
-      info[li] = u32x4{L.pk_len, L.out_len, uint32_t(L.row), L.flags | (L.is_row << 8)};
-      mark[li] = L.is_row;
-      if (L.row >= 0 && T.t.hit) T.t.hit[L.row] = 1;  // (every writer stores the same byte)
-      n_cr += L.lone_cr;
-      n_miss += L.missed;
+      tally.line(L, li, info, mark, T.t.hit);
     });
   });
-  if (blockIdx.x == 0 && threadIdx.x == 0) mark[n_lines] = 0;  // the scan leaves the row count there
-  wave_add(&counts[AVDB_TXTUPD_COUNT_LONE_CR], n_cr);
-  wave_add(&counts[AVDB_TXTUPD_COUNT_NOT_IN_FILE], n_miss);
-}
-
-__global__ __launch_bounds__(kBlock) void k_txtupd_compact(const uint64_t* __restrict__ starts, size_t text_bytes,
-                                                           size_t n_lines, const u32x4* __restrict__ info,
-                                                           const uint64_t* __restrict__ row_of, TxtUpdCols o,
-                                                           unsigned long long* __restrict__ counts) {
-  uint64_t bytes = 0;
-  uint32_t n_bad = 0, n_host = 0;
-  for (size_t li = size_t(blockIdx.x) * blockDim.x + threadIdx.x; li < n_lines; li += size_t(gridDim.x) * blockDim.x) {
-    const u32x4 v = info[li];
-    if (!((v.w >> 8) & 1u)) continue;
-    const uint64_t r = row_of[li];  // r < n_lines: at most one row per line
-    uint64_t s = starts[li];
-    if (s > text_bytes) s = text_bytes;
-    const uint32_t flags = v.w & 0xFFu;
-    o.row_start[r] = s;
-    o.pk_len[r] = v.x;
-    o.out_len[r] = v.y;
-    o.match[r] = int32_t(v.z);
-    o.flags[r] = uint8_t(flags);
-    bytes += v.y;
-    n_bad += (flags & AVDB_TXTUPD_BAD) != 0;
-    n_host += (flags & AVDB_TXTUPD_TABLE_HOST) != 0;
-  }
-  if (blockIdx.x == 0 && threadIdx.x == 0) {
-    // (k_txtupd_lines, which counts the records without a table row, has finished)
-    const uint64_t rows = row_of[n_lines];
-    counts[AVDB_TXTUPD_COUNT_ROWS] = rows;
-    counts[AVDB_TXTUPD_COUNT_SKIPPED_LINES] = n_lines - rows - counts[AVDB_TXTUPD_COUNT_NOT_IN_FILE];
-  }
-  wave_add(&counts[AVDB_TXTUPD_COUNT_OUT_BYTES], bytes);
-  wave_add(&counts[AVDB_TXTUPD_COUNT_BAD], n_bad);
-  wave_add(&counts[AVDB_TXTUPD_COUNT_HOST_ROWS], n_host);
-}
-
-__global__ __launch_bounds__(kBlock) void k_txtupd_write(const uint8_t* __restrict__ text, size_t text_bytes,
-                                                         txt::Table T, uint32_t adsp, TxtUpdCols o,
-                                                         const uint64_t* __restrict__ row_off, size_t n_rows,
-                                                         uint8_t* __restrict__ out,
-                                                         const uint64_t* __restrict__ totals) {
-  __shared__ uint64_t s_out[kTxtWriteStage / 8];
-  auto tb = [&](uint64_t pos) -> uint32_t { return pos < text_bytes ? uint32_t(text[pos]) : 0u; };
-  rows::write_rows<kTxtWriteStage>(
-      row_off, n_rows, out, totals, s_out,
-      [&](size_t r) { return UpdRow{o.row_start[r], o.pk_len[r], o.out_len[r], o.flags[r], o.match[r]}; },
-      [&](const UpdRow& row, auto put) { txt::render_update_row(row, T, adsp != 0, tb, put); });
+  tally.finish(mark, n_lines, counts);
 }
 
 // ---- K19c ---------------------------------------------------------------------------------
@@ -379,18 +272,9 @@ __global__ __launch_bounds__(kBlock) void k_txtdir_write(const uint8_t* __restri
 
 using namespace avdb;
 
-// K19a's workspace: K16a's (16 bytes of info per line, three scanned arrays for the write pass)
-static rows::Layout table_layout(size_t n_lines) { return rows::layout(n_lines, 16, 32); }
-static rows::Layout upd_layout(size_t n_lines) { return rows::layout(n_lines, 16); }
-
-static TxtEntScans ent_scans(char* w, const rows::Layout& L, size_t n_lines) {
-  auto* base = reinterpret_cast<uint64_t*>(w + L.extra);
-  return TxtEntScans{base, base + (n_lines + 1), base + 2 * (n_lines + 1)};
-}
-
 extern "C" int avdb_txt_table_workspace_size(size_t text_bytes, size_t n_lines, size_t* bytes) {
   (void)text_bytes;
-  return rows::workspace_size(table_layout(n_lines).total, bytes);
+  return rows::workspace_size(tables::table_layout(n_lines).total, bytes);
 }
 
 extern "C" int avdb_txt_update_workspace_size(size_t text_bytes, size_t n_lines, size_t* bytes) {
@@ -403,61 +287,21 @@ extern "C" int avdb_txt_direct_workspace_size(size_t text_bytes, size_t n_lines,
   return rows::workspace_size(upd_layout(n_lines).total, bytes);
 }
 
-static bool ent_null(const TxtEntCols& o) { return !o.start || !o.alts || !o.key_bytes || !o.body_len || !o.flags; }
-
-static const char* table_size_error(const void* ctx, const uint8_t* text, size_t text_bytes, size_t n_lines,
-                                    const Shape& S, const TxtEntCols& o, const uint64_t* counts) {
-  if (!ctx || !counts) return "null argument";
-  if (const char* err = txt::shape_error(S)) return err;
-  if (const char* err = lines::text_args_error(text, text_bytes, n_lines)) return err;
-  if (n_lines && ent_null(o)) return "null output array";
-  return nullptr;
-}
-
-static const char* table_write_error(const void* ctx, const uint8_t* text, size_t text_bytes, size_t n_lines,
-                                     size_t n_entries, size_t n_rows, const Shape& S, const TxtEntCols& o,
-                                     const uint8_t* keys, size_t key_cap, const uint64_t* key_off, const uint8_t* body,
-                                     size_t body_cap, const RowCols& R, const uint64_t* totals) {
-  if (!ctx || !totals || !key_off) return "null argument";
-  if (const char* err = txt::shape_error(S)) return err;
-  if (const char* err = rows::text_rows_error(text, text_bytes, n_lines, n_entries)) return err;
-  if (n_rows > n_entries) return "more rows than entries (an entry is one row)";
-  if (n_entries && ent_null(o)) return "null entry array";
-  if (n_rows && (!R.json_off || !R.json_len || !R.line_start || !R.flags)) return "null row array";
-  if (const char* err = rows::out_error(keys, key_cap)) return err;
-  return rows::out_error(body, body_cap);
-}
-
 extern "C" int avdb_txt_table_size(avdb_ctx* ctx, const uint8_t* text, size_t text_bytes, size_t n_lines,
                                    uint32_t skip_lines, uint32_t n_fields, uint32_t id_col, uint32_t key_col,
                                    uint64_t* ent_start, uint32_t* ent_alts, uint32_t* ent_key_bytes,
                                    uint32_t* ent_body_len, uint8_t* ent_flags, uint64_t* counts, void* workspace,
                                    size_t workspace_bytes, void* stream) {
   const Shape S{skip_lines, n_fields, id_col, key_col};
-  const TxtEntCols o{ent_start, ent_alts, ent_key_bytes, ent_body_len, ent_flags};
-  if (const char* err = table_size_error(ctx, text, text_bytes, n_lines, S, o, counts)) {
-    avdb_set_error("avdb_txt_table_size: %s", err);
-    return AVDB_EINVAL;
-  }
-  const rows::Layout L = table_layout(n_lines);
+  const EntCols o{ent_start, ent_alts, ent_key_bytes, ent_body_len, ent_flags};
   hipStream_t s = static_cast<hipStream_t>(stream);
-  if (int e = rows::begin_size("avdb_txt_table_size", ctx, L.total, n_lines, workspace, workspace_bytes, counts,
-                               AVDB_TXT_N_COUNTS, s))
-    return e;
-  if (n_lines == 0) return AVDB_OK;
-  char* w = static_cast<char*>(workspace);
-  auto* info = reinterpret_cast<u32x4*>(w + L.info);
-  auto* cnt = reinterpret_cast<unsigned long long*>(counts);
-  const unsigned grid = stream_grid(n_lines, kBlock, 4096);
-  auto mark = [&](const uint64_t* starts, uint64_t* marks) {
-    hipLaunchKernelGGL(k_txt_lines, dim3(grid), dim3(kBlock), 0, s, text, text_bytes, starts, n_lines, S, info, marks,
-                       cnt);
-  };
-  if (int e = lines::number_rows(text, text_bytes, n_lines, w, L, s, "k_txt_lines", mark)) return e;
-  hipLaunchKernelGGL(k_txt_compact, dim3(grid), dim3(kBlock), 0, s, reinterpret_cast<const uint64_t*>(w + L.starts),
-                     text_bytes, n_lines, info, reinterpret_cast<const uint64_t*>(w + L.row_of), o, cnt);
-  AVDB_LAUNCH_CHECK("k_txt_compact");
-  return AVDB_OK;
+  return tables::table_size<TxtBuild>(
+      {"avdb_txt_table_size", ctx, {text, text_bytes, n_lines}, nullptr, txt::shape_error(S)}, o, counts,
+      AVDB_TXT_N_COUNTS, {workspace, workspace_bytes, s}, "k_txt_lines",
+      [&](unsigned grid, const uint64_t* starts, u32x4* info, uint64_t* marks, unsigned long long* cnt) {
+        hipLaunchKernelGGL(k_txt_lines, dim3(grid), dim3(kBlock), 0, s, text, text_bytes, starts, n_lines, S, info, marks,
+                           cnt);
+      });
 }
 
 extern "C" int avdb_txt_table_write(avdb_ctx* ctx, const uint8_t* text, size_t text_bytes, size_t n_lines,
@@ -470,41 +314,23 @@ extern "C" int avdb_txt_table_write(avdb_ctx* ctx, const uint8_t* text, size_t t
                                     uint8_t* row_flags, uint64_t* totals, void* workspace, size_t workspace_bytes,
                                     void* stream) {
   const Shape S{skip_lines, n_fields, id_col, key_col};
-  const TxtEntCols o{const_cast<uint64_t*>(ent_start), const_cast<uint32_t*>(ent_alts),
-                     const_cast<uint32_t*>(ent_key_bytes), const_cast<uint32_t*>(ent_body_len),
-                     const_cast<uint8_t*>(ent_flags)};
+  const EntCols o{const_cast<uint64_t*>(ent_start), const_cast<uint32_t*>(ent_alts),
+                  const_cast<uint32_t*>(ent_key_bytes), const_cast<uint32_t*>(ent_body_len),
+                  const_cast<uint8_t*>(ent_flags)};
   const RowCols R{key_off, row_body_off, row_body_len, row_line_start, row_flags, n_rows};
-  if (const char* err = table_write_error(ctx, text, text_bytes, n_lines, n_entries, n_rows, S, o, keys, key_cap,
-                                          key_off, body, body_cap, R, totals)) {
-    avdb_set_error("avdb_txt_table_write: %s", err);
-    return AVDB_EINVAL;
-  }
-  const rows::Layout L = table_layout(n_lines);
-  if (int e = n_lines ? lines::workspace_error("avdb_txt_table_write", L.total, workspace, workspace_bytes) : 0) return e;
-  AVDB_HIP_TRY(hipSetDevice(ctx->device));
   hipStream_t s = static_cast<hipStream_t>(stream);
-  if (n_lines == 0) {  // no entries and no workspace: zero totals
-    AVDB_HIP_TRY(hipMemsetAsync(totals, 0, 32, s));
-    AVDB_HIP_TRY(hipMemsetAsync(key_off, 0, 8, s));
-    return AVDB_OK;
-  }
-  char* w = static_cast<char*>(workspace);
-  const TxtEntScans sc = ent_scans(w, L, n_lines);
-  if (n_entries) {
-    if (int e = scan::exclusive_u64(ent_alts, sc.row, n_entries, w + L.scan, L.scan_bytes, s)) return e;
-    if (int e = scan::exclusive_u64(ent_key_bytes, sc.key, n_entries, w + L.scan, L.scan_bytes, s)) return e;
-    if (int e = scan::exclusive_u64(ent_body_len, sc.body, n_entries, w + L.scan, L.scan_bytes, s)) return e;
-  }
-  hipLaunchKernelGGL(k_txt_totals, dim3(1), dim3(kWave), 0, s, o, sc, n_entries, uint64_t(n_rows), uint64_t(key_cap),
-                     uint64_t(body_cap), key_off, totals);
-  AVDB_LAUNCH_CHECK("k_txt_totals");
-  if (n_entries == 0) return AVDB_OK;
-  const unsigned grid = stream_grid(n_entries, kBlock, 2048);
-  hipLaunchKernelGGL(k_txt_keys, dim3(grid), dim3(kBlock), 0, s, text, text_bytes, S, o, sc, n_entries, R, keys, totals);
-  AVDB_LAUNCH_CHECK("k_txt_keys");
-  hipLaunchKernelGGL(k_txt_bodies, dim3(grid), dim3(kBlock), 0, s, text, text_bytes, S, o, sc, n_entries, body, totals);
-  AVDB_LAUNCH_CHECK("k_txt_bodies");
-  return AVDB_OK;
+  return tables::table_write<TxtBuild>(
+      {"avdb_txt_table_write", ctx, {text, text_bytes, n_lines}, nullptr, txt::shape_error(S)}, n_entries,
+      n_rows, o, {keys, key_cap, body, body_cap, R, totals}, {workspace, workspace_bytes, s}, "k_txt_keys",
+      [&](unsigned grid, const EntScans& sc) {
+        hipLaunchKernelGGL(k_txt_keys, dim3(grid), dim3(kBlock), 0, s, text, text_bytes, S, o, sc, n_entries, R, keys,
+                           totals);
+      },
+      "k_txt_bodies",
+      [&](unsigned grid, const EntScans& sc) {
+        hipLaunchKernelGGL(k_txt_bodies, dim3(grid), dim3(kBlock), 0, s, text, text_bytes, S, o, sc, n_entries, body,
+                           totals);
+      });
 }
 
 // ---- K19a on the host --------------------------------------------------------------------
@@ -513,39 +339,17 @@ extern "C" int avdb_txt_table_size_host(const avdb_ctx* ctx, const uint8_t* text
                                         uint64_t* ent_start, uint32_t* ent_alts, uint32_t* ent_key_bytes,
                                         uint32_t* ent_body_len, uint8_t* ent_flags, uint64_t* counts) {
   const Shape S{skip_lines, n_fields, id_col, key_col};
-  const TxtEntCols o{ent_start, ent_alts, ent_key_bytes, ent_body_len, ent_flags};
-  if (const char* err = table_size_error(ctx, text, text_bytes, n_lines, S, o, counts)) {
-    avdb_set_error("avdb_txt_table_size_host: %s", err);
-    return AVDB_EINVAL;
-  }
-  memset(counts, 0, 8 * AVDB_TXT_N_COUNTS);
-  if (n_lines == 0) return AVDB_OK;
-  const std::vector<uint64_t> starts = lines::host_line_starts(text, text_bytes, n_lines);
-  uint64_t n = 0;
-  for (size_t li = 0; li < n_lines; ++li) {
-    uint64_t s, e;
-    bool nl;
-    lines::line_span(text, text_bytes, starts.data(), n_lines, li, &s, &e, &nl);
-    const txt::Line L = txt::parse_line(text + s, e - s, nl, li >= S.skip_lines, S);
-    counts[AVDB_TXT_COUNT_LONE_CR] += L.lone_cr;
-    counts[AVDB_TXT_COUNT_SKIPPED_LINES] += !L.data;
-    if (!L.data) continue;
-    const bool dev = !L.flags;
-    ent_start[n] = s;
-    ent_alts[n] = dev;
-    ent_key_bytes[n] = dev ? L.key_n : 0u;
-    ent_body_len[n] = dev ? txt::body_len(L) : 0u;
-    ent_flags[n] = uint8_t(L.flags);
-    counts[AVDB_TXT_COUNT_ROWS] += ent_alts[n];
-    counts[AVDB_TXT_COUNT_KEY_BYTES] += ent_key_bytes[n];
-    counts[AVDB_TXT_COUNT_JSON_BYTES] += ent_body_len[n];
-    counts[AVDB_TXT_COUNT_HOST_LINES] += (L.flags & AVDB_TXT_LINE_HOST) != 0;
-    counts[AVDB_TXT_COUNT_BAD] += (L.flags & AVDB_TXT_LINE_BAD) != 0;
-    ++n;
-  }
-  counts[AVDB_TXT_COUNT_ENTRIES] = n;
-  counts[AVDB_TXT_COUNT_LINES] = n_lines;
-  return AVDB_OK;
+  const EntCols o{ent_start, ent_alts, ent_key_bytes, ent_body_len, ent_flags};
+  return tables::table_size_host<TxtBuild>(
+      {"avdb_txt_table_size_host", ctx, {text, text_bytes, n_lines}, nullptr, txt::shape_error(S)}, o,
+      counts, AVDB_TXT_N_COUNTS, [&](size_t li, const uint8_t* line, uint64_t len, bool nl, lof::Entry* E) {
+        const txt::Line L = txt::parse_line(line, len, nl, li >= S.skip_lines, S);
+        const bool dev = L.data && !L.flags;
+        *E = lof::Entry{dev ? 1u : 0u, dev ? L.key_n : 0u, dev ? txt::body_len(L) : 0u, L.flags};
+        counts[AVDB_TXT_COUNT_LONE_CR] += L.lone_cr;
+        counts[AVDB_TXT_COUNT_SKIPPED_LINES] += !L.data;
+        return L.data != 0;
+      });
 }
 
 extern "C" int avdb_txt_table_write_host(const avdb_ctx* ctx, const uint8_t* text, size_t text_bytes, size_t n_lines,
@@ -557,44 +361,19 @@ extern "C" int avdb_txt_table_write_host(const avdb_ctx* ctx, const uint8_t* tex
                                          uint64_t* row_body_off, uint32_t* row_body_len, uint64_t* row_line_start,
                                          uint8_t* row_flags, uint64_t* totals) {
   const Shape S{skip_lines, n_fields, id_col, key_col};
-  const TxtEntCols o{const_cast<uint64_t*>(ent_start), const_cast<uint32_t*>(ent_alts),
-                     const_cast<uint32_t*>(ent_key_bytes), const_cast<uint32_t*>(ent_body_len),
-                     const_cast<uint8_t*>(ent_flags)};
+  const EntCols o{const_cast<uint64_t*>(ent_start), const_cast<uint32_t*>(ent_alts),
+                  const_cast<uint32_t*>(ent_key_bytes), const_cast<uint32_t*>(ent_body_len),
+                  const_cast<uint8_t*>(ent_flags)};
   const RowCols R{key_off, row_body_off, row_body_len, row_line_start, row_flags, n_rows};
-  if (const char* err = table_write_error(ctx, text, text_bytes, n_lines, n_entries, n_rows, S, o, keys, key_cap,
-                                          key_off, body, body_cap, R, totals)) {
-    avdb_set_error("avdb_txt_table_write_host: %s", err);
-    return AVDB_EINVAL;
-  }
-  uint64_t r = 0, k = 0, j = 0;
-  for (size_t e = 0; e < n_entries; ++e) {
-    r += ent_alts[e];
-    k += ent_key_bytes[e];
-    j += ent_body_len[e];
-  }
-  const bool over = k > key_cap || j > body_cap || r != n_rows;
-  totals[0] = k;
-  totals[1] = j;
-  totals[2] = r;
-  totals[3] = over;
-  if (over) {
-    avdb_set_error("avdb_txt_table_write_host: %llu key bytes, %llu body bytes and %llu rows required",
-                   (unsigned long long)k, (unsigned long long)j, (unsigned long long)r);
-    return AVDB_ERANGE;
-  }
-  key_off[n_rows] = k;
-  r = k = j = 0;
-  for (size_t e = 0; e < n_entries; ++e) {
-    const EntryRow E{ent_start[e], ent_alts[e], ent_key_bytes[e], ent_body_len[e], ent_flags[e], r, k, j};
-    txt::with_line_at(text, text_bytes, E.start, [&](const uint8_t* line, uint64_t len, bool nl, bool have) {
-      txt::render_entry_key(line, len, nl, have, E, R, S, [&](uint32_t i, uint32_t c) { keys[k + i] = uint8_t(c); });
-      txt::render_entry_body(line, len, nl, have, E, S, [&](uint32_t i, uint32_t c) { body[j + i] = uint8_t(c); });
-    });
-    r += E.alts;
-    k += E.key_bytes;
-    j += E.json_len;
-  }
-  return AVDB_OK;
+  return tables::table_write_host<TxtBuild>(
+      {"avdb_txt_table_write_host", ctx, {text, text_bytes, n_lines}, nullptr, txt::shape_error(S)},
+      n_entries, n_rows, o, {keys, key_cap, body, body_cap, R, totals}, "body",
+      [&](const EntryRow& E, auto put_key, auto put_body) {
+        txt::with_line_at(text, text_bytes, E.start, [&](const uint8_t* line, uint64_t len, bool nl, bool have) {
+          txt::render_entry_key(line, len, nl, have, E, R, S, put_key);
+          txt::render_entry_body(line, len, nl, have, E, S, put_body);
+        });
+      });
 }
 
 // ---- K19b's entries -------------------------------------------------------------------------
@@ -602,45 +381,14 @@ static const char* table_view(const avdb_txt_table* t, txt::Table* T) {
   if (!t) return "null table";
   if (t->struct_size != sizeof(avdb_txt_table)) return "avdb_txt_table of another size";
   memset(T, 0, sizeof(*T));
-  if (t->n_rows >= 0x7FFFFFFFull) return "too many table rows";
-  if (t->n_rows == 0) return nullptr;
-  if (!t->keys || !t->key_off || !t->keyset || !t->body_off || !t->body_len || !t->flags || (t->body_bytes && !t->body))
-    return "null table array";
-  const uint64_t slots = keyset::slots(size_t(t->n_rows));
-  if (t->keyset_bytes < slots * 12) return "key set smaller than avdb_keyset_workspace_size";
-  T->t.n_rows = t->n_rows;
-  T->t.keys = t->keys;
-  T->t.key_off = t->key_off;
-  T->t.tkey = static_cast<const unsigned long long*>(t->keyset);
-  T->t.tidx = reinterpret_cast<const uint32_t*>(T->t.tkey + slots);
-  T->t.mask = slots - 1;
-  T->t.json = t->body;
-  T->t.json_bytes = t->body_bytes;
-  T->t.json_off = t->body_off;
-  T->t.json_len = t->body_len;
-  T->t.hit = t->hit;
-  T->flags = t->flags;
-  return nullptr;
+  const char* err = tables::fill_table_view(&T->t, t->n_rows, t->keys, t->key_off, t->keyset, t->keyset_bytes, t->body,
+                                            t->body_bytes, t->body_off, t->body_len, t->hit, !t->flags);
+  if (!err && t->n_rows) T->flags = t->flags;
+  return err;
 }
 
-static bool upd_null(const TxtUpdCols& o) { return !o.row_start || !o.pk_len || !o.match || !o.out_len || !o.flags; }
-
-static const char* upd_size_error(const void* ctx, const uint8_t* text, size_t text_bytes, size_t n_lines,
-                                  uint32_t key_col, const TxtUpdCols& o, const uint64_t* counts) {
-  if (!ctx || !counts) return "null argument";
-  if (key_col != 1 && key_col != 2) return "key_col out of range (1: metaseq_id, 2: ref_snp_id)";
-  if (const char* err = lines::text_args_error(text, text_bytes, n_lines)) return err;
-  if (n_lines && upd_null(o)) return "null output array";
-  return nullptr;
-}
-
-static const char* upd_write_error(const void* ctx, const uint8_t* text, size_t text_bytes, size_t n_lines,
-                                   size_t n_rows, const TxtUpdCols& o, const uint8_t* out, size_t out_cap,
-                                   const uint64_t* row_off, const uint64_t* totals) {
-  if (!ctx || !totals || !row_off) return "null argument";
-  if (const char* err = rows::text_rows_error(text, text_bytes, n_lines, n_rows)) return err;
-  if (n_rows && upd_null(o)) return "null row array";
-  return rows::out_error(out, out_cap);
+static const char* key_col_error(uint32_t key_col) {
+  return key_col != 1 && key_col != 2 ? "key_col out of range (1: metaseq_id, 2: ref_snp_id)" : nullptr;
 }
 
 extern "C" int avdb_txt_update_size(avdb_ctx* ctx, const uint8_t* text, size_t text_bytes, size_t n_lines,
@@ -649,34 +397,17 @@ extern "C" int avdb_txt_update_size(avdb_ctx* ctx, const uint8_t* text, size_t t
                                     uint32_t* out_len, uint8_t* row_flags, uint64_t* counts, void* workspace,
                                     size_t workspace_bytes, void* stream) {
   txt::Table T;
-  const TxtUpdCols o{row_start, pk_len, match, out_len, row_flags};
   const char* err = table_view(table, &T);
-  if (!err) err = upd_size_error(ctx, text, text_bytes, n_lines, key_col, o, counts);
-  if (err) {
-    avdb_set_error("avdb_txt_update_size: %s", err);
-    return AVDB_EINVAL;
-  }
-  const rows::Layout L = upd_layout(n_lines);
   hipStream_t s = static_cast<hipStream_t>(stream);
-  if (int e = rows::begin_size("avdb_txt_update_size", ctx, L.total, n_lines, workspace, workspace_bytes, counts,
-                               AVDB_TXTUPD_N_COUNTS, s))
-    return e;
-  if (n_lines == 0) return AVDB_OK;
-  char* w = static_cast<char*>(workspace);
-  auto* info = reinterpret_cast<u32x4*>(w + L.info);
-  auto* cnt = reinterpret_cast<unsigned long long*>(counts);
-  const unsigned grid = stream_grid(n_lines, kBlock, 4096);
   const uint32_t adsp = (flags & AVDB_TXT_ADSP) != 0;
-  auto mark = [&](const uint64_t* starts, uint64_t* marks) {
-    hipLaunchKernelGGL(k_txtupd_lines, dim3(grid), dim3(kBlock), 0, s, text, text_bytes, starts, n_lines, T,
-                       contig_mask, key_col, adsp, info, marks, cnt);
-  };
-  if (int e = lines::number_rows(text, text_bytes, n_lines, w, L, s, "k_txtupd_lines", mark)) return e;
-  hipLaunchKernelGGL(k_txtupd_compact, dim3(grid), dim3(kBlock), 0, s,
-                     reinterpret_cast<const uint64_t*>(w + L.starts), text_bytes, n_lines, info,
-                     reinterpret_cast<const uint64_t*>(w + L.row_of), o, cnt);
-  AVDB_LAUNCH_CHECK("k_txtupd_compact");
-  return AVDB_OK;
+  return tables::update_size<TxtJoin>(
+      {"avdb_txt_update_size", ctx, {text, text_bytes, n_lines}, err, key_col_error(key_col)},
+      UpdCols{row_start, pk_len, match, out_len, row_flags}, counts, AVDB_TXTUPD_N_COUNTS,
+      {workspace, workspace_bytes, s}, "k_txtupd_lines",
+      [&](unsigned grid, const uint64_t* starts, u32x4* info, uint64_t* marks, unsigned long long* cnt) {
+        hipLaunchKernelGGL(k_txtupd_lines, dim3(grid), dim3(kBlock), 0, s, text, text_bytes, starts, n_lines, T,
+                           contig_mask, key_col, adsp, info, marks, cnt);
+      });
 }
 
 extern "C" int avdb_txt_update_write(avdb_ctx* ctx, const uint8_t* text, size_t text_bytes, size_t n_lines,
@@ -685,24 +416,14 @@ extern "C" int avdb_txt_update_write(avdb_ctx* ctx, const uint8_t* text, size_t 
                                      const uint32_t* out_len, const uint8_t* row_flags, uint8_t* out, size_t out_cap,
                                      uint64_t* row_off, uint64_t* totals, void* workspace, size_t workspace_bytes,
                                      void* stream) {
-  txt::Table T;
-  const TxtUpdCols o{const_cast<uint64_t*>(row_start), const_cast<uint32_t*>(pk_len), const_cast<int32_t*>(match),
-                     const_cast<uint32_t*>(out_len), const_cast<uint8_t*>(row_flags)};
-  const char* err = table_view(table, &T);
-  if (!err) err = upd_write_error(ctx, text, text_bytes, n_lines, n_rows, o, out, out_cap, row_off, totals);
-  if (err) {
-    avdb_set_error("avdb_txt_update_write: %s", err);
-    return AVDB_EINVAL;
-  }
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  if (int e = rows::begin_write("avdb_txt_update_write", ctx, upd_layout(n_lines), n_lines, workspace, workspace_bytes,
-                                out_len, n_rows, out_cap, row_off, totals, s))
-    return e;
-  if (n_rows == 0) return AVDB_OK;
-  hipLaunchKernelGGL(k_txtupd_write, dim3(stream_grid(n_rows, kBlock, 2048)), dim3(kBlock), 0, s, text, text_bytes, T,
-                     uint32_t((flags & AVDB_TXT_ADSP) != 0), o, row_off, n_rows, out, totals);
-  AVDB_LAUNCH_CHECK("k_txtupd_write");
-  return AVDB_OK;
+  TxtRows render{};
+  const char* err = table_view(table, &render.T);
+  render.adsp = (flags & AVDB_TXT_ADSP) != 0;
+  const UpdCols o{const_cast<uint64_t*>(row_start), const_cast<uint32_t*>(pk_len), const_cast<int32_t*>(match),
+                  const_cast<uint32_t*>(out_len), const_cast<uint8_t*>(row_flags)};
+  return tables::update_write<kTxtWriteStage>({"avdb_txt_update_write", ctx, {text, text_bytes, n_lines}, err}, n_rows, o,
+                                              {out, out_cap, row_off, totals},
+                                              {workspace, workspace_bytes, static_cast<hipStream_t>(stream)}, render);
 }
 
 extern "C" int avdb_txt_update_size_host(const avdb_ctx* ctx, const uint8_t* text, size_t text_bytes, size_t n_lines,
@@ -710,40 +431,14 @@ extern "C" int avdb_txt_update_size_host(const avdb_ctx* ctx, const uint8_t* tex
                                          uint32_t flags, uint64_t* row_start, uint32_t* pk_len, int32_t* match,
                                          uint32_t* out_len, uint8_t* row_flags, uint64_t* counts) {
   txt::Table T;
-  const TxtUpdCols o{row_start, pk_len, match, out_len, row_flags};
   const char* err = table_view(table, &T);
-  if (!err) err = upd_size_error(ctx, text, text_bytes, n_lines, key_col, o, counts);
-  if (err) {
-    avdb_set_error("avdb_txt_update_size_host: %s", err);
-    return AVDB_EINVAL;
-  }
-  memset(counts, 0, 8 * AVDB_TXTUPD_N_COUNTS);
-  if (n_lines == 0) return AVDB_OK;
-  const std::vector<uint64_t> starts = lines::host_line_starts(text, text_bytes, n_lines);
   const bool adsp = (flags & AVDB_TXT_ADSP) != 0;
-  uint64_t rows = 0;
-  for (size_t li = 0; li < n_lines; ++li) {
-    uint64_t s, e;
-    bool nl;
-    lines::line_span(text, text_bytes, starts.data(), n_lines, li, &s, &e, &nl);
-    const txt::UpdLine L = txt::scan_export_line(text + s, e - s, nl, contig_mask, key_col, adsp, T);
-    counts[AVDB_TXTUPD_COUNT_LONE_CR] += L.lone_cr;
-    counts[AVDB_TXTUPD_COUNT_NOT_IN_FILE] += L.missed;
-    if (L.row >= 0 && T.t.hit) T.t.hit[L.row] = 1;
-    if (!L.is_row) continue;
-    row_start[rows] = s;
-    pk_len[rows] = L.pk_len;
-    match[rows] = L.row;
-    out_len[rows] = L.out_len;
-    row_flags[rows] = uint8_t(L.flags);
-    ++rows;
-    counts[AVDB_TXTUPD_COUNT_OUT_BYTES] += L.out_len;
-    counts[AVDB_TXTUPD_COUNT_BAD] += (L.flags & AVDB_TXTUPD_BAD) != 0;
-    counts[AVDB_TXTUPD_COUNT_HOST_ROWS] += (L.flags & AVDB_TXTUPD_TABLE_HOST) != 0;
-  }
-  counts[AVDB_TXTUPD_COUNT_ROWS] = rows;
-  counts[AVDB_TXTUPD_COUNT_SKIPPED_LINES] = n_lines - rows - counts[AVDB_TXTUPD_COUNT_NOT_IN_FILE];
-  return AVDB_OK;
+  return tables::update_size_host<TxtJoin>(
+      {"avdb_txt_update_size_host", ctx, {text, text_bytes, n_lines}, err, key_col_error(key_col)},
+      UpdCols{row_start, pk_len, match, out_len, row_flags}, counts, AVDB_TXTUPD_N_COUNTS, err ? nullptr : T.t.hit,
+      [&](const uint8_t* line, uint64_t len, bool nl) {
+        return txt::scan_export_line(line, len, nl, contig_mask, key_col, adsp, T);
+      });
 }
 
 extern "C" int avdb_txt_update_write_host(const avdb_ctx* ctx, const uint8_t* text, size_t text_bytes, size_t n_lines,
@@ -751,24 +446,13 @@ extern "C" int avdb_txt_update_write_host(const avdb_ctx* ctx, const uint8_t* te
                                           const uint64_t* row_start, const uint32_t* pk_len, const int32_t* match,
                                           const uint32_t* out_len, const uint8_t* row_flags, uint8_t* out,
                                           size_t out_cap, uint64_t* row_off, uint64_t* totals) {
-  txt::Table T;
-  const TxtUpdCols o{const_cast<uint64_t*>(row_start), const_cast<uint32_t*>(pk_len), const_cast<int32_t*>(match),
-                     const_cast<uint32_t*>(out_len), const_cast<uint8_t*>(row_flags)};
-  const char* err = table_view(table, &T);
-  if (!err) err = upd_write_error(ctx, text, text_bytes, n_lines, n_rows, o, out, out_cap, row_off, totals);
-  if (err) {
-    avdb_set_error("avdb_txt_update_write_host: %s", err);
-    return AVDB_EINVAL;
-  }
-  if (int e = rows::host_row_offsets("avdb_txt_update_write_host", out_len, n_rows, out_cap, row_off, totals)) return e;
-  const bool adsp = (flags & AVDB_TXT_ADSP) != 0;
-  auto tb = [&](uint64_t pos) -> uint32_t { return pos < text_bytes ? uint32_t(text[pos]) : 0u; };
-  for (size_t r = 0; r < n_rows; ++r) {
-    const UpdRow row{row_start[r], pk_len[r], out_len[r], row_flags[r], match[r]};
-    const uint64_t off = row_off[r];
-    txt::render_update_row(row, T, adsp, tb, [&](uint32_t k, uint32_t c) { out[off + k] = uint8_t(c); });
-  }
-  return AVDB_OK;
+  TxtRows render{};
+  const char* err = table_view(table, &render.T);
+  render.adsp = (flags & AVDB_TXT_ADSP) != 0;
+  const UpdCols o{const_cast<uint64_t*>(row_start), const_cast<uint32_t*>(pk_len), const_cast<int32_t*>(match),
+                  const_cast<uint32_t*>(out_len), const_cast<uint8_t*>(row_flags)};
+  return tables::update_write_host({"avdb_txt_update_write_host", ctx, {text, text_bytes, n_lines}, err}, n_rows, o,
+                                   {out, out_cap, row_off, totals}, render);
 }
 
 // ---- K19c's entries -------------------------------------------------------------------------

@@ -528,26 +528,43 @@ def _copy_text(column: bytes) -> str:
     return out.decode("utf-8")
 
 
-def qc_update_rows(engine, text, table, update_existing: bool = False, contigs=None):
-    import json
-    if table.text.device != engine.device:
-        raise ValueError("QC table lives on another device than this engine")
+def _table_update_rows(engine, text, table, name: str, count_names, bad_bit: int, size_extra, write_extra,
+                       fix_host_rows=None):
+    """The export join K16b, K17b and K19b share: entry ``avdb_<name>_size`` / ``_write`` with ``size_extra`` and
+    ``write_extra`` arguments behind the table view, one row per record of the export whose id the table holds.
+    ``fix_host_rows(sp, row_start, out_len, flags, n, cnt)`` settles the rows the device left to the host between
+    the passes and returns how many of them it dropped (their ``out_len`` zeroed, ``cnt`` brought up to date).
+    Returns ``(rows kept, text, row_off, match, flags, cnt)``."""
     view = table.view()
     vp = ctypes.byref(view)
-    sp = SlabPass(engine, text, "qc_update", "avdb_qc_update_workspace_size")
+    sp = SlabPass(engine, text, name, f"avdb_{name}_workspace_size")
     row_start, pk_len, match, out_len, flags = sp.cols(torch.int64, torch.int32, torch.int32, torch.int32, torch.uint8)
-    counts = engine.empty(N.QCUPD_N_COUNTS, torch.int64)
-    sp.call("avdb_qc_update_size", sp.tp, sp.nb, sp.n_lines, vp, E.existing_contig_mask(contigs),
-            N.QCUPD_UPDATE_EXISTING if update_existing else 0, row_start, pk_len, match, out_len, flags, counts)
-    cnt = sp.counts(counts, N.QCUPD_COUNTS)
+    counts = engine.empty(len(count_names), torch.int64)
+    sp.call(f"avdb_{name}_size", sp.tp, sp.nb, sp.n_lines, vp, *size_extra, row_start, pk_len, match, out_len, flags,
+            counts)
+    cnt = sp.counts(counts, count_names)
     if cnt["lone_cr"]:
         sp.raise_lone_cr(cnt["lone_cr"], "pass does not")
     n = cnt["rows"]
     if cnt["bad"]:
-        sp.raise_bad_metaseq(row_start, flags, N.QCUPD_BAD, n, cnt["bad"])
+        sp.raise_bad_metaseq(row_start, flags, bad_bit, n, cnt["bad"])
+    dropped = fix_host_rows(sp, row_start, out_len, flags, n, cnt) if fix_host_rows and cnt["host_rows"] else 0
     out_bytes = cnt["out_bytes"]
-    dropped = 0
-    if cnt["host_rows"]:
+    out_text = engine.empty(max(1, out_bytes), torch.uint8)
+    row_off = engine.empty(n + 1, torch.int64)
+    totals = engine.empty(2, torch.int64)
+    sp.call(f"avdb_{name}_write", sp.tp, sp.nb, sp.n_lines, n, vp, *write_extra, row_start, pk_len, match, out_len, flags,
+            out_text, out_bytes, row_off, totals)
+    sp.check_totals(f"avdb_{name}_write", totals.cpu().tolist(), out_bytes, "rows")
+    return n - dropped, out_text[:out_bytes], row_off, match[:n], flags[:n], cnt
+
+
+def qc_update_rows(engine, text, table, update_existing: bool = False, contigs=None):
+    import json
+    if table.text.device != engine.device:
+        raise ValueError("QC table lives on another device than this engine")
+
+    def fix_host_rows(sp, row_start, out_len, flags, n, cnt):
         # the columns the device does not scan: json.loads and Python's `in`, as load():49 has it
         host_rows = torch.nonzero(flags[:n] & N.QCUPD_ROW_HOST).flatten()
         release = table.release.decode("ascii")
@@ -566,44 +583,23 @@ def qc_update_rows(engine, text, table, update_existing: bool = False, contigs=N
                 drop.append(r)
         if drop:
             drop_t = torch.tensor(drop, dtype=torch.int64, device=engine.device)
-            out_bytes -= int(out_len[drop_t].sum())
+            cnt["out_bytes"] -= int(out_len[drop_t].sum())
             out_len[drop_t] = 0
-            dropped = len(drop)
-            cnt["skipped"] += dropped
-    cnt["out_bytes"] = out_bytes
-    out_text = engine.empty(max(1, out_bytes), torch.uint8)
-    row_off = engine.empty(n + 1, torch.int64)
-    totals = engine.empty(2, torch.int64)
-    sp.call("avdb_qc_update_write", sp.tp, sp.nb, sp.n_lines, n, vp, row_start, pk_len, match, out_len, flags,
-            out_text, out_bytes, row_off, totals)
-    sp.check_totals("avdb_qc_update_write", totals.cpu().tolist(), out_bytes, "rows")
-    return E.QcUpdateRows(n - dropped, out_text[:out_bytes], row_off, match[:n], flags[:n], cnt)
+            cnt["skipped"] += len(drop)
+        return len(drop)
+
+    return E.QcUpdateRows(*_table_update_rows(
+        engine, text, table, "qc_update", N.QCUPD_COUNTS, N.QCUPD_BAD,
+        (E.existing_contig_mask(contigs), N.QCUPD_UPDATE_EXISTING if update_existing else 0), (), fix_host_rows))
 
 
 def lof_update_rows(engine, text, table, update_existing: bool = False, contigs=None):
     if table.text.device != engine.device:
         raise ValueError("LOF table lives on another device than this engine")
-    view = table.view()
-    vp = ctypes.byref(view)
-    sp = SlabPass(engine, text, "lof_update", "avdb_lof_update_workspace_size")
-    row_start, pk_len, match, out_len, flags = sp.cols(torch.int64, torch.int32, torch.int32, torch.int32, torch.uint8)
-    counts = engine.empty(N.LOFUPD_N_COUNTS, torch.int64)
-    sp.call("avdb_lof_update_size", sp.tp, sp.nb, sp.n_lines, vp, E.existing_contig_mask(contigs),
-            N.LOFUPD_UPDATE_EXISTING if update_existing else 0, row_start, pk_len, match, out_len, flags, counts)
-    cnt = sp.counts(counts, N.LOFUPD_COUNTS)
-    if cnt["lone_cr"]:
-        sp.raise_lone_cr(cnt["lone_cr"], "pass does not")
-    n = cnt["rows"]
-    if cnt["bad"]:
-        sp.raise_bad_metaseq(row_start, flags, N.LOFUPD_BAD, n, cnt["bad"])
-    out_bytes = cnt["out_bytes"]
-    out_text = engine.empty(max(1, out_bytes), torch.uint8)
-    row_off = engine.empty(n + 1, torch.int64)
-    totals = engine.empty(2, torch.int64)
-    sp.call("avdb_lof_update_write", sp.tp, sp.nb, sp.n_lines, n, vp, row_start, pk_len, match, out_len, flags,
-            out_text, out_bytes, row_off, totals)
-    sp.check_totals("avdb_lof_update_write", totals.cpu().tolist(), out_bytes, "rows")
-    return E.LofUpdateRows(n, out_text[:out_bytes], row_off, match[:n], cnt)
+    n, out, row_off, match, _, cnt = _table_update_rows(
+        engine, text, table, "lof_update", N.LOFUPD_COUNTS, N.LOFUPD_BAD,
+        (E.existing_contig_mask(contigs), N.LOFUPD_UPDATE_EXISTING if update_existing else 0), ())
+    return E.LofUpdateRows(n, out, row_off, match, cnt)
 
 
 def _txt_header(engine, text, variant_id_type: str):
@@ -631,28 +627,11 @@ def txt_update_rows(engine, text, table, id_type: str = "METASEQ", adsp: bool = 
                          "txt_direct_rows)")
     if table.text.device != engine.device:
         raise ValueError("the table lives on another device than this engine")
-    view = table.view()
-    vp = ctypes.byref(view)
     key_col, flags_arg = (1 if id_type == "METASEQ" else 2), (N.TXT_ADSP if adsp else 0)
-    sp = SlabPass(engine, text, "txt_update", "avdb_txt_update_workspace_size")
-    row_start, pk_len, match, out_len, flags = sp.cols(torch.int64, torch.int32, torch.int32, torch.int32, torch.uint8)
-    counts = engine.empty(N.TXTUPD_N_COUNTS, torch.int64)
-    sp.call("avdb_txt_update_size", sp.tp, sp.nb, sp.n_lines, vp, E.existing_contig_mask(contigs), key_col, flags_arg,
-            row_start, pk_len, match, out_len, flags, counts)
-    cnt = sp.counts(counts, N.TXTUPD_COUNTS)
-    if cnt["lone_cr"]:
-        sp.raise_lone_cr(cnt["lone_cr"], "pass does not")
-    n = cnt["rows"]
-    if cnt["bad"]:
-        sp.raise_bad_metaseq(row_start, flags, N.TXTUPD_BAD, n, cnt["bad"])
-    out_bytes = cnt["out_bytes"]
-    out_text = engine.empty(max(1, out_bytes), torch.uint8)
-    row_off = engine.empty(n + 1, torch.int64)
-    totals = engine.empty(2, torch.int64)
-    sp.call("avdb_txt_update_write", sp.tp, sp.nb, sp.n_lines, n, vp, flags_arg, row_start, pk_len, match, out_len,
-            flags, out_text, out_bytes, row_off, totals)
-    sp.check_totals("avdb_txt_update_write", totals.cpu().tolist(), out_bytes, "rows")
-    return E.TxtUpdateRows(n, out_text[:out_bytes], row_off, match[:n], cnt)
+    n, out, row_off, match, _, cnt = _table_update_rows(
+        engine, text, table, "txt_update", N.TXTUPD_COUNTS, N.TXTUPD_BAD,
+        (E.existing_contig_mask(contigs), key_col, flags_arg), (flags_arg,))
+    return E.TxtUpdateRows(n, out, row_off, match, cnt)
 
 
 def txt_direct_rows(engine, text, adsp: bool = False):

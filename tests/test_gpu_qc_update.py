@@ -300,6 +300,25 @@ def test_g5_errors_raise_on_the_device(engine):
     assert json.loads(Q.table_tuples(t)[0][1]) == {"r1": {"info": {"AC": 1}, "filter": "PASS", "qual": 50, "format": "GT"}}
 
 
+def test_g5_write_entry_on_an_empty_slab(engine, host):
+    """avdb_qc_table_write on a zero-byte slab (no lines, so no scans and no kernels), totals and
+    key_off poisoned: without rows zero totals and key_off[0] = 0; a row that nothing bears out sets
+    totals[3] and leaves key_off alone, the device entry returning OK and the host entry ERANGE."""
+    poison = int(np.frombuffer(b"\xA5" * 8, dtype=np.int64)[0])
+    for eng, over_rc in ((engine, 0), (host, N.AVDB_ERANGE)):
+        suffix, tail = Q._runner(eng, "qc_table", "avdb_qc_table_workspace_size", 0, 0)
+        full = lambda n, dt: torch.full((n * torch.empty(0, dtype=dt).element_size(),), 0xA5,  # noqa: E731
+                                        dtype=torch.uint8, device=eng.device).view(dt)
+        for n_rows, want_rc, want, want_off in ((0, 0, [0, 0, 0, 0], 0), (1, over_rc, [0, 0, 0, 1], poison)):
+            ents = [full(1, torch.int64)] + [full(1, torch.int32) for _ in range(3)] + [full(1, torch.uint8)]
+            key_off, totals = full(n_rows + 1, torch.int64), full(4, torch.int64)
+            rc = Q._call(eng, "avdb_qc_table_write" + suffix, None, 0, 0, 0, n_rows, b"r1", 2, *ents,
+                         full(8, torch.uint8), 0, key_off, full(8, torch.uint8), 0, full(1, torch.int64),
+                         full(1, torch.int32), full(1, torch.int64), full(1, torch.uint8), totals, *tail)
+            assert (rc, totals.cpu().tolist(), int(key_off[0])) == (want_rc, want, want_off), (eng.host_only, n_rows)
+            assert key_off.cpu().tolist()[1:] == [poison] * n_rows
+
+
 # ---- 6: bgzip input ------------------------------------------------------------------------------------
 def test_g6_bgzip_pair_through_read_whole(engine, host, tmp_path):
     from annotatedvdb_amd import bgzf

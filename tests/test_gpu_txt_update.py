@@ -350,6 +350,28 @@ def test_g5_empty_inputs(engine, host):
         assert rc == 0 and totals == [0, 0] and out["row_off"][0] == 0
 
 
+def test_g5_write_entry_on_an_empty_slab(engine, host):
+    """avdb_txt_table_write on a zero-byte slab (no lines, so no scans and no kernels), totals and
+    key_off poisoned: without rows zero totals and key_off[0] = 0; a row is refused up front (an entry
+    is one row, and there is none), on the device and on the host, and nothing is written."""
+    from annotatedvdb_amd.slab_passes import SlabPass
+    poison = int(np.frombuffer(b"\xA5" * 8, dtype=np.int64)[0])
+    for eng in (engine, host):
+        sp = SlabPass(eng, b"", "txt_table", "avdb_txt_table_workspace_size")
+        for n_rows, want_rc, want, want_off in ((0, 0, [0, 0, 0, 0], 0), (1, N.AVDB_EINVAL, [poison] * 4, poison)):
+            ents = [T.poisoned(eng, 1, dt) for dt in (torch.int64, torch.int32, torch.int32, torch.int32, torch.uint8)]
+            key_off, totals = T.poisoned(eng, n_rows + 1, torch.int64), T.poisoned(eng, 4, torch.int64)
+            try:
+                rc = sp.call("avdb_txt_table_write", sp.tp, sp.nb, sp.n_lines, 0, n_rows, 0, 2, 0, 0, *ents,
+                             T.poisoned(eng, 8, torch.uint8), 0, key_off, T.poisoned(eng, 8, torch.uint8), 0,
+                             T.poisoned(eng, 1, torch.int64), T.poisoned(eng, 1, torch.int32),
+                             T.poisoned(eng, 1, torch.int64), T.poisoned(eng, 1, torch.uint8), totals)
+            except N.NativeError as e:
+                rc = e.rc
+                assert "more rows than entries" in str(e)
+            assert (rc or 0, totals.cpu().tolist(), int(key_off[0])) == (want_rc, want, want_off), (eng.host_only, n_rows)
+
+
 # ---- 6: bgzip input ------------------------------------------------------------------------------------
 def test_g6_bgzip_pair_through_the_driver(engine, tmp_path):
     import bgzf_common as Z
