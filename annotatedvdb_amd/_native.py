@@ -107,6 +107,11 @@ TXTUPD_N_COUNTS = len(TXTUPD_COUNTS)
 TXTDIR_COUNTS = ("rows", "lines", "skipped_lines", "host_rows", "bad", "out_bytes",
                  "lone_cr")  # AVDB_TXTDIR_COUNT_*, by slot
 TXTDIR_N_COUNTS = len(TXTDIR_COUNTS)
+VEP_MAX_CSQ, VEP_MAX_DEPTH, VEP_GRID_WAVES = 512, 64, 2048  # AVDB_VEP_*
+VEP_REASONS = ("whitespace", "structure", "depth", "duplicate_key", "element", "bytes", "repeated_term", "no_terms",
+               "unknown_term", "unknown_combination", "too_many")  # why a line is the host's, by flags - 1
+VEP_COUNTS = ("lines", "host_lines", "consequences") + VEP_REASONS  # AVDB_VEP_COUNT_*, by slot
+VEP_N_COUNTS = len(VEP_COUNTS)
 EXPVCF_ROW_HOST, EXPVCF_BAD, EXPVCF_DROPPED = 1, 2, 4  # AVDB_EXPVCF_* row flags
 EXPVCF_STREAM_VCF, EXPVCF_STREAM_INVALID = 0, 1
 EXPVCF_COUNTS = ("valid", "invalid", "skipped_lines", "filtered", "bad", "lone_cr", "vcf_bytes",
@@ -197,6 +202,19 @@ class TxtTableView(ctypes.Structure):
                          body_off, body_len, flags, hit)
 
 
+class VepTableView(ctypes.Structure):
+    """avdb_vep_table (include/avdb.h); ``struct_size`` is filled in."""
+    _fields_ = [("struct_size", ctypes.c_uint32), ("n_terms", ctypes.c_uint32), ("term_words", ctypes.c_void_p),
+                ("term_off", ctypes.c_void_p), ("term_len", ctypes.c_void_p), ("slot_mask", ctypes.c_void_p),
+                ("slot_entry", ctypes.c_void_p), ("n_slots", ctypes.c_uint32), ("n_entries", ctypes.c_uint32),
+                ("rank_order", ctypes.c_void_p), ("coding_mask", ctypes.c_uint64)]
+
+    def __init__(self, n_terms: int = 0, term_words=None, term_off=None, term_len=None, slot_mask=None,
+                 slot_entry=None, n_slots: int = 0, n_entries: int = 0, rank_order=None, coding_mask: int = 0):
+        super().__init__(ctypes.sizeof(VepTableView), n_terms, term_words, term_off, term_len, slot_mask, slot_entry,
+                         n_slots, n_entries, rank_order, coding_mask)
+
+
 class LineResult(ctypes.Structure):
     """avdb_line_result (include/avdb.h)."""
     _fields_ = [(name, ctypes.c_uint32) for name in ("state", "flags", "copy_bytes", "map_bytes", "n_rec", "n_rows",
@@ -253,6 +271,8 @@ EXPORTED_SYMBOLS = [
     "avdb_txt_update_size_host", "avdb_txt_update_write_host",
     "avdb_txt_direct_workspace_size", "avdb_txt_direct_size", "avdb_txt_direct_write",
     "avdb_txt_direct_size_host", "avdb_txt_direct_write_host",
+    "avdb_vep_table_build", "avdb_vep_index_workspace_size", "avdb_vep_index_size", "avdb_vep_index_write",
+    "avdb_vep_index_size_host", "avdb_vep_index_write_host",
 ]
 
 
@@ -447,6 +467,13 @@ def _sig(lib):
     f.avdb_txt_direct_size.argtypes = f.avdb_txt_direct_size_host.argtypes + [P, SZ, P]
     f.avdb_txt_direct_write_host.argtypes = [P, P, SZ, SZ, SZ, U32, U32, U32, U32, P, P, P, P, SZ, P, P]
     f.avdb_txt_direct_write.argtypes = f.avdb_txt_direct_write_host.argtypes + [P, SZ, P]
+    VT = ctypes.POINTER(VepTableView)
+    f.avdb_vep_table_build.argtypes = [P, U32, P, SZ, P, P, SZ]
+    f.avdb_vep_index_workspace_size.argtypes = [SZ, SZ, ctypes.POINTER(SZ)]
+    f.avdb_vep_index_size_host.argtypes = [P, P, SZ, SZ, VT] + [P] * 8
+    f.avdb_vep_index_size.argtypes = f.avdb_vep_index_size_host.argtypes + [P, SZ, P]
+    f.avdb_vep_index_write_host.argtypes = [P, P, SZ, SZ, VT, P, P, P, SZ] + [P] * 12
+    f.avdb_vep_index_write.argtypes = f.avdb_vep_index_write_host.argtypes + [P, SZ, P]
     for name in EXPORTED_SYMBOLS:
         if name not in ("avdb_last_error",):
             getattr(f, name).restype = I32

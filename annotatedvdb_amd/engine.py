@@ -1662,6 +1662,22 @@ class Engine:
         host entries run the same per-line code."""
         return slab_passes.lof_update_rows(self, text, table, update_existing, contigs)
 
+    # -- K18a: VEP consequences, ranked and sorted ---------------------------------------
+    def vep_consequences(self, text, ranking) -> "VepConsequences":
+        """K18a: a '\\n'-separated slab of VEP ``--json`` output (bytes, numpy ``uint8``, a ``uint8``
+        tensor, or a path: plain, gzip or bgzip through :func:`annotatedvdb_amd.bgzf.read_whole`)
+        and a ranking (:class:`~annotatedvdb_amd.vep_consequences.ConsequenceRanking`, or what it
+        takes) -> :class:`~annotatedvdb_amd.vep_consequences.VepConsequences` on this engine's
+        device: for every element of a line's four ``<type>_consequences`` arrays what
+        ``VepJsonParser.adsp_rank_and_sort_consequences`` adds to it (``vep_parser.py:145-175``),
+        and the order the elements end up in per type and allele.  Lines outside the device subset
+        (``counts['host_lines']``, by reason in ``counts``: DESIGN.md, K18a) get blank rows, and
+        :meth:`VepConsequences.ranked` answers them through
+        :func:`~annotatedvdb_amd.vep_consequences.vep_line`.  Three syncs: the line count, the size
+        pass's counts, the end.  On a host-only engine the library's host entries run the same
+        per-block code."""
+        return slab_passes.vep_consequences(self, text, ranking)
+
     # -- K17: ADSP QC pVCF update rows --------------------------------------------------
     def qc_table_build(self, text, version: str, header_fields=None) -> "QcTable":
         """K17a: a '\\n'-separated slab of an ADSP QC pVCF (bytes, numpy ``uint8`` or a ``uint8``

@@ -1,8 +1,8 @@
 """The passes over a '\\n'-separated text slab behind :class:`~annotatedvdb_amd.engine.Engine`:
 K10a ``cadd_table_build``, K12 ``existing_table_build``, K13 ``cadd_update_rows``, K14
 ``export_vcf``, K15 ``split_vcf``, K16 ``lof_table_build`` / ``lof_update_rows``, K17
-``qc_table_build`` / ``qc_update_rows`` and K19 ``txt_table_build`` / ``txt_update_rows`` /
-``txt_direct_rows``.
+``qc_table_build`` / ``qc_update_rows``, K18a ``vep_consequences`` and K19 ``txt_table_build`` /
+``txt_update_rows`` / ``txt_direct_rows``.
 
 The two-pass ones have one shape: line count -> size pass -> its counts to the host (second
 sync) -> the rows the device leaves to the host rendered here -> outputs allocated -> write
@@ -512,6 +512,39 @@ def qc_table_build(engine, text, version, header_fields=None):
     parts = _alt_table_build(engine, text, "qc_table", N.QC_COUNTS, (release, len(release)), host_line,
                              not plain or b"Infinity" in release)
     return E.QcTable(*parts, release)
+
+
+def vep_consequences(engine, text, ranking):
+    import os
+    from . import bgzf
+    from .vep_consequences import ConsequenceRanking, VepConsequences
+    if not isinstance(ranking, ConsequenceRanking):
+        ranking = ConsequenceRanking(ranking)
+    if isinstance(text, (str, os.PathLike)):
+        text = bgzf.read_whole(os.fspath(text), engine)
+    tab = ranking.table(engine)
+    sp = SlabPass(engine, text, "vep_index", "avdb_vep_index_workspace_size")
+    n_csq, flags, types, in_start, in_len, id_start, id_len = sp.cols(torch.int32, torch.uint8, torch.uint8, torch.int64,
+                                                                      torch.int32, torch.int64, torch.int32)
+    counts = engine.empty(N.VEP_N_COUNTS, torch.int64)
+    sp.call("avdb_vep_index_size", sp.tp, sp.nb, sp.n_lines, tab.ref, n_csq, flags, types, in_start, in_len, id_start,
+            id_len, counts)
+    cnt = sp.counts(counts, N.VEP_COUNTS)
+    total = cnt["consequences"]
+    per_line = n_csq[:sp.n_lines].long()
+    csq_off = torch.zeros(sp.m, dtype=torch.int64, device=engine.device)
+    csq_off[:sp.n_lines] = torch.cumsum(per_line, 0) - per_line
+    cols = [engine.empty(max(1, total), dt) for dt in (torch.uint8, torch.int32, torch.int64, torch.int32, torch.int64,
+                                                       torch.int32, torch.int64, torch.int32, torch.uint8, torch.int32,
+                                                       torch.uint8)]
+    totals = engine.empty(2, torch.int64)
+    sp.call("avdb_vep_index_write", sp.tp, sp.nb, sp.n_lines, tab.ref, n_csq, flags, csq_off, total, *cols, totals)
+    got = totals.cpu().tolist()
+    if got != [total, 0]:
+        raise N.NativeError("avdb_vep_index_write" + sp.suffix, N.AVDB_ERANGE,
+                            f"{got[0]} rows written, {got[1]} line(s) that differ from the size pass's {total} rows")
+    return VepConsequences(engine, sp.text, ranking, sp.n_lines, cnt,
+                           (n_csq, flags, types, in_start, in_len, id_start, id_len, csq_off), cols)
 
 
 def _copy_text(column: bytes) -> str:

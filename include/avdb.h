@@ -1571,6 +1571,88 @@ int avdb_txt_direct_write_host(const avdb_ctx* ctx, const uint8_t* text, size_t 
                                const uint64_t* row_start, const uint32_t* out_len, const uint8_t* row_flags,
                                uint8_t* out, size_t out_cap, uint64_t* row_off, uint64_t* totals);
 
+/* ---- K18a: the consequences of VEP's JSON lines, ranked and sorted ---------------------------
+ * `text` is a '\n'-separated slab of VEP --json output: one compact JSON object a line ("\r\n"
+ * ends a line too).  For every element of the line's four <type>_consequences arrays (transcript,
+ * regulatory_feature, motif_feature, intergenic: types 0..3) the pass gives what
+ * VepJsonParser.adsp_rank_and_sort_consequences adds (vep_parser.py:145-175): its index in its
+ * array (vep_consequence_order_num), the ranking entry of its consequence_terms (rank) and whether
+ * one of them is a coding term (consequence_is_coding); and the order the elements end up in: type,
+ * then the variant_allele's first appearance in the array, then (rank, index).  One wave reads a
+ * line, 64 bytes a step.
+ * avdb_vep_table: the ranking.  Term i is term_len[i] bytes, zero-padded to whole words at
+ * term_words[term_off[i]]; at most 64 terms.  A combination is the mask of its terms' numbers; the
+ * open-addressed slots (n_slots a power of two, slot_entry -1 for none, avdb_vep_table_build fills
+ * them on the host) map a mask to its ranking entry, rank_order[entry] is the entry's place among
+ * the distinct ranks, coding_mask the coding terms.  The arrays live where the entry runs.
+ *   1. avdb_vep_index_size: per line its consequences n_csq, a flags byte, `types` (bit t: the line
+ *      has the <type>_consequences key of type t, were its array empty), and the spans of the
+ *      top-level strings `input` and `id` (the bytes between the quotes; length -1: none); counts
+ *      (AVDB_VEP_N_COUNTS x u64, set by the call).  flags 0: the device answers the line; else 1 +
+ *      the first of the reasons it is left to the caller, counted under AVDB_VEP_COUNT_REASON0 +
+ *      reason: 0 whitespace outside a string, 1 no '{' first or brackets or a string left open, 2
+ *      depth beyond AVDB_VEP_MAX_DEPTH, 3 a key of interest twice at the top level, 4 an element
+ *      that is no object with one variant_allele string and one consequence_terms array of strings
+ *      (or a <type>_consequences value that is no array of objects), 5 a backslash or a byte >=
+ *      0x80 in a key, an allele or a term, 6 a term twice in one element, 7 no terms, 8 a term the
+ *      table lacks, 9 a combination it lacks, 10 more than AVDB_VEP_MAX_CSQ consequences.  JSON
+ *      grammar is not checked beyond this.
+ *   2. avdb_vep_index_write (csq_off: the exclusive sums of n_csq, n_csq_total their sum): row
+ *      csq_off[line] + k is the line's k-th consequence in text order: type, order number, the
+ *      element's span, the allele's span, term mask, ranking entry, coding flag.  sorted[csq_off
+ *      [line] + p] is the k of the consequence at place p of the order above, head[...+ p] 1 when
+ *      it is the first of its (type, allele) group.  A line with flags != 0 gets blank rows (entry
+ *      -1, sorted the identity).  totals[0]: rows written, totals[1]: lines whose count differs
+ *      from n_csq or whose rows do not fit (nothing is written for them).
+ * Workspace: avdb_vep_index_workspace_size bytes, 256-byte aligned; the device entries enqueue on
+ * `stream`, the _host forms run the same per-block code on host arrays. */
+#define AVDB_VEP_MAX_CSQ 512   /* consequences of a line the device sorts (quadratic per line, 20 KiB of LDS per wave) */
+#define AVDB_VEP_MAX_DEPTH 64
+#define AVDB_VEP_GRID_WAVES 2048 /* at most this many waves (one a workgroup) read a slab: wave w the lines w, w + waves, ... */
+#define AVDB_VEP_N_REASONS 11
+#define AVDB_VEP_COUNT_LINES 0
+#define AVDB_VEP_COUNT_HOST_LINES 1
+#define AVDB_VEP_COUNT_CSQ 2
+#define AVDB_VEP_COUNT_REASON0 3
+#define AVDB_VEP_N_COUNTS 14
+typedef struct avdb_vep_table {
+  uint32_t struct_size; /* sizeof(avdb_vep_table) */
+  uint32_t n_terms;
+  const uint64_t* term_words;
+  const uint32_t* term_off; /* per term, in words */
+  const uint32_t* term_len; /* per term, in bytes */
+  const uint64_t* slot_mask;
+  const int32_t* slot_entry;
+  uint32_t n_slots;
+  uint32_t n_entries;
+  const uint32_t* rank_order; /* per entry */
+  uint64_t coding_mask;
+} avdb_vep_table;
+/* host arrays: the slots of n_entries masks (the first entry of a mask stays); AVDB_EINVAL for more
+ * than 64 terms, a mask with a term beyond n_terms, or fewer than 2 * n_entries slots */
+int avdb_vep_table_build(const avdb_ctx* ctx, uint32_t n_terms, const uint64_t* entry_mask, size_t n_entries,
+                         uint64_t* slot_mask, int32_t* slot_entry, size_t n_slots);
+int avdb_vep_index_workspace_size(size_t text_bytes, size_t n_lines, size_t* bytes);
+int avdb_vep_index_size(avdb_ctx* ctx, const uint8_t* text, size_t text_bytes, size_t n_lines,
+                        const avdb_vep_table* table, uint32_t* n_csq, uint8_t* flags, uint8_t* types, uint64_t* input_start,
+                        int32_t* input_len, uint64_t* id_start, int32_t* id_len, uint64_t* counts, void* workspace,
+                        size_t workspace_bytes, void* stream);
+int avdb_vep_index_write(avdb_ctx* ctx, const uint8_t* text, size_t text_bytes, size_t n_lines,
+                         const avdb_vep_table* table, const uint32_t* n_csq, const uint8_t* flags,
+                         const uint64_t* csq_off, size_t n_csq_total, uint8_t* type, int32_t* order,
+                         uint64_t* el_start, uint32_t* el_len, uint64_t* al_start, uint32_t* al_len, uint64_t* mask,
+                         int32_t* entry, uint8_t* coding, int32_t* sorted, uint8_t* head, uint64_t* totals,
+                         void* workspace, size_t workspace_bytes, void* stream);
+int avdb_vep_index_size_host(const avdb_ctx* ctx, const uint8_t* text, size_t text_bytes, size_t n_lines,
+                             const avdb_vep_table* table, uint32_t* n_csq, uint8_t* flags, uint8_t* types, uint64_t* input_start,
+                             int32_t* input_len, uint64_t* id_start, int32_t* id_len, uint64_t* counts);
+int avdb_vep_index_write_host(const avdb_ctx* ctx, const uint8_t* text, size_t text_bytes, size_t n_lines,
+                              const avdb_vep_table* table, const uint32_t* n_csq, const uint8_t* flags,
+                              const uint64_t* csq_off, size_t n_csq_total, uint8_t* type, int32_t* order,
+                              uint64_t* el_start, uint32_t* el_len, uint64_t* al_start, uint32_t* al_len,
+                              uint64_t* mask, int32_t* entry, uint8_t* coding, int32_t* sorted, uint8_t* head,
+                              uint64_t* totals);
+
 /* ---- host-side formatting of kernel outputs -------------------------------
  * ltree path text (<= AVDB_MAX_PATH bytes).  Returns the length written (no
  * NUL terminator counted; one is written if cap allows), or a negative code. */
