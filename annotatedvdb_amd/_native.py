@@ -112,6 +112,13 @@ VEP_REASONS = ("whitespace", "structure", "depth", "duplicate_key", "element", "
                "unknown_term", "unknown_combination", "too_many")  # why a line is the host's, by flags - 1
 VEP_COUNTS = ("lines", "host_lines", "consequences") + VEP_REASONS  # AVDB_VEP_COUNT_*, by slot
 VEP_N_COUNTS = len(VEP_COUNTS)
+VEPROWS_LINE_HOST, VEPROWS_ROW_FIRST, VEPROWS_MAX_TOKEN = 1, 4, 32  # AVDB_VEPROWS_*
+VEPROWS_REASONS = VEP_REASONS + ("no_input", "input_fields", "escape", "byte",
+                                 "token")  # why a line is the host's, by (entry flags >> 2) - 1
+VEPROWS_COUNTS = ("rows", "lines", "host_lines", "bad", "key_bytes", "json_bytes", "lone_cr",
+                  "entries") + VEPROWS_REASONS  # AVDB_VEPROWS_COUNT_*, by slot
+VEPROWS_N_COUNTS = len(VEPROWS_COUNTS)
+VEPUPD_UPDATE_EXISTING, VEPUPD_ADSP = 1, 2  # AVDB_VEPUPD_* (the join's counts and row flags are K16b's: LOFUPD_*)
 EXPVCF_ROW_HOST, EXPVCF_BAD, EXPVCF_DROPPED = 1, 2, 4  # AVDB_EXPVCF_* row flags
 EXPVCF_STREAM_VCF, EXPVCF_STREAM_INVALID = 0, 1
 EXPVCF_COUNTS = ("valid", "invalid", "skipped_lines", "filtered", "bad", "lone_cr", "vcf_bytes",
@@ -215,6 +222,19 @@ class VepTableView(ctypes.Structure):
                          n_slots, n_entries, rank_order, coding_mask)
 
 
+class VepRowsIn(ctypes.Structure):
+    """avdb_vep_rows_in (include/avdb.h); ``struct_size`` is filled in."""
+    _fields_ = [("struct_size", ctypes.c_uint32), ("n_ranks", ctypes.c_uint32), ("n_csq_total", ctypes.c_uint64),
+                ("rank_text", ctypes.c_void_p), ("rank_text_bytes", ctypes.c_uint64), ("rank_off", ctypes.c_void_p)] + \
+               [(name, ctypes.c_void_p) for name in ("line_flags", "n_csq", "csq_off", "input_start", "input_len", "type",
+                                                     "order", "el_start", "el_len", "al_start", "al_len", "entry",
+                                                     "coding", "sorted", "el_rlen")]
+
+    def __init__(self, n_ranks: int = 0, n_csq_total: int = 0, rank_text=None, rank_text_bytes: int = 0, rank_off=None,
+                 *arrays):
+        super().__init__(ctypes.sizeof(VepRowsIn), n_ranks, n_csq_total, rank_text, rank_text_bytes, rank_off, *arrays)
+
+
 class LineResult(ctypes.Structure):
     """avdb_line_result (include/avdb.h)."""
     _fields_ = [(name, ctypes.c_uint32) for name in ("state", "flags", "copy_bytes", "map_bytes", "n_rec", "n_rows",
@@ -273,6 +293,10 @@ EXPORTED_SYMBOLS = [
     "avdb_txt_direct_size_host", "avdb_txt_direct_write_host",
     "avdb_vep_table_build", "avdb_vep_index_workspace_size", "avdb_vep_index_size", "avdb_vep_index_write",
     "avdb_vep_index_size_host", "avdb_vep_index_write_host",
+    "avdb_vep_rows_table_workspace_size", "avdb_vep_rows_table_size", "avdb_vep_rows_table_write",
+    "avdb_vep_rows_table_size_host", "avdb_vep_rows_table_write_host", "avdb_vep_rows_token_ok_host",
+    "avdb_vep_rows_update_workspace_size", "avdb_vep_rows_update_size", "avdb_vep_rows_update_write",
+    "avdb_vep_rows_update_size_host", "avdb_vep_rows_update_write_host",
 ]
 
 
@@ -474,6 +498,18 @@ def _sig(lib):
     f.avdb_vep_index_size.argtypes = f.avdb_vep_index_size_host.argtypes + [P, SZ, P]
     f.avdb_vep_index_write_host.argtypes = [P, P, SZ, SZ, VT, P, P, P, SZ] + [P] * 12
     f.avdb_vep_index_write.argtypes = f.avdb_vep_index_write_host.argtypes + [P, SZ, P]
+    VR = ctypes.POINTER(VepRowsIn)
+    f.avdb_vep_rows_table_workspace_size.argtypes = [SZ, SZ, ctypes.POINTER(SZ)]
+    f.avdb_vep_rows_table_size_host.argtypes = [P, P, SZ, SZ, VR] + [P] * 6
+    f.avdb_vep_rows_table_size.argtypes = f.avdb_vep_rows_table_size_host.argtypes + [P, SZ, P]
+    f.avdb_vep_rows_table_write_host.argtypes = [P, P, SZ, SZ, SZ, SZ, VR, P, P, P, P, P, P, SZ, P, P, SZ, P, P, P, P, P]
+    f.avdb_vep_rows_table_write.argtypes = f.avdb_vep_rows_table_write_host.argtypes + [P, SZ, P]
+    f.avdb_vep_rows_token_ok_host.argtypes = [P, SZ]
+    f.avdb_vep_rows_update_workspace_size.argtypes = [SZ, SZ, ctypes.POINTER(SZ)]
+    f.avdb_vep_rows_update_size_host.argtypes = [P, P, SZ, SZ, LT, U32, U32, ctypes.c_uint64, P, P, P, P, P, P]
+    f.avdb_vep_rows_update_size.argtypes = f.avdb_vep_rows_update_size_host.argtypes + [P, SZ, P]
+    f.avdb_vep_rows_update_write_host.argtypes = [P, P, SZ, SZ, SZ, LT, U32, ctypes.c_uint64, P, P, P, P, P, P, SZ, P, P]
+    f.avdb_vep_rows_update_write.argtypes = f.avdb_vep_rows_update_write_host.argtypes + [P, SZ, P]
     for name in EXPORTED_SYMBOLS:
         if name not in ("avdb_last_error",):
             getattr(f, name).restype = I32

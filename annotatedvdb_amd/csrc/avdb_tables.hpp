@@ -1,7 +1,8 @@
-// The skeleton K16 (avdb_lof.hip), K17 (avdb_qc.hip) and K19 (avdb_txt.hip) share, on avdb_rows.hpp:
-// a table build over the annotation file and an export join against that table, each a size entry
-// and a write entry with a _host twin.  A pass keeps what differs: its line kernels, its key and
-// JSON (K19: body) write kernels, its stage sizes, its renderers, and one policy struct per half.
+// The skeleton K16 (avdb_lof.hip), K17 (avdb_qc.hip), K18b (avdb_vep_rows.hip) and K19 (avdb_txt.hip)
+// share, on avdb_rows.hpp: a table build over the annotation file and an export join against that
+// table, each a size entry and a write entry with a _host twin.  A pass keeps what differs: its
+// line kernels, its key and JSON (K19: body) write kernels, its stage sizes, its renderers, and one
+// policy struct per half.
 //   the table build (avdb_*_table_size / _write)
 //     the pass's line kernel: info[li] = {alts, key_bytes, json_len, class | flags << 8}, a mark per entry
 //     k_compact<P>    one lane per line: an entry's columns to its entry number; the counts

@@ -201,15 +201,21 @@ AVDB_HD void init_state(State& st) {
   st.input_len = st.id_len = -1;
 }
 
-// the quotes that count, the string mask and the brackets outside strings; carries st over the edge
-AVDB_HD Masks derive(const Raw& r, State& st) {
-  // a byte is escaped when the run of backslashes that ends before it has odd length
-  const uint64_t b = r.bs & ~st.esc;  // (an escaped backslash escapes nothing)
+// the bytes a backslash escapes: those behind a run of backslashes of odd length.  esc carries over
+// the block edge (bit 0: the next block's first byte is escaped)
+AVDB_HD uint64_t escaped_of(uint64_t bs, uint64_t& esc) {
+  const uint64_t b = bs & ~esc;  // (an escaped backslash escapes nothing)
   const uint64_t starts = b & ~(b << 1);
   const uint64_t even_runs = (b + (starts & kEven)) ^ b;  // the runs that start on an even bit, and the bit past each
   const uint64_t follows = b << 1;
-  const uint64_t escaped = (follows & even_runs & ~kEven) | (follows & ~even_runs & kEven) | st.esc;
-  st.esc = (b >> 63) & ~(even_runs >> 63) & 1;  // a run to the edge that started on an odd bit: 64 - start is odd
+  const uint64_t escaped = (follows & even_runs & ~kEven) | (follows & ~even_runs & kEven) | esc;
+  esc = (b >> 63) & ~(even_runs >> 63) & 1;  // a run to the edge that started on an odd bit: 64 - start is odd
+  return escaped;
+}
+
+// the quotes that count, the string mask and the brackets outside strings; carries st over the edge
+AVDB_HD Masks derive(const Raw& r, State& st) {
+  const uint64_t escaped = escaped_of(r.bs, st.esc);
   Masks m;
   m.quotes = r.qt & ~escaped;
   m.in_str = prefix_xor(m.quotes) ^ st.in_str;

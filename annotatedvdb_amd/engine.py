@@ -183,6 +183,20 @@ class LofUpdateRows:
 
 
 @dataclass
+class VepRowsTable(LofTable):
+    """What K18b makes of VEP ``--json`` output (:meth:`Engine.vep_rows_table_build`): :class:`LofTable`'s
+    members for one row per ALT allele of every line's ``input``; row ``k``'s
+    ``json[json_off[k]:json_off[k] + json_len[k]]`` is its own body,
+    ``<adsp_most_severe_consequence><TAB><adsp_ranked_consequences>`` as ``json.dumps`` prints them
+    (``{}`` for ``None``); ``counts`` by ``N.VEPROWS_COUNTS``; ``ranking`` the
+    :class:`~annotatedvdb_amd.vep_consequences.ConsequenceRanking`; ``unranked`` the lines that need a
+    re-rank and gave no rows, ``(line number, id, combination)``."""
+    ranking: object = None
+    unranked: list = None
+    _keep: tuple = ()  # K18a's arrays and the rank text, which the table's build read
+
+
+@dataclass
 class QcTable(LofTable):
     """What K17a makes of an ADSP QC pVCF (:meth:`Engine.qc_table_build`): :class:`LofTable`'s
     members for one row per ALT allele of every line, ``json`` holding each line's
@@ -1677,6 +1691,33 @@ class Engine:
         pass's counts, the end.  On a host-only engine the library's host entries run the same
         per-block code."""
         return slab_passes.vep_consequences(self, text, ranking)
+
+    # -- K18b: VEP consequence update rows ------------------------------------------------
+    def vep_rows_table_build(self, text, ranking) -> "VepRowsTable":
+        """K18b: VEP ``--json`` output (what :meth:`vep_consequences` takes) and a ranking ->
+        :class:`VepRowsTable` on this engine's device: K18a's pass, then one row per ALT allele of the
+        VCF line in every line's ``input``, keyed by its metaseq id ``chrom:pos:ref:alt``, its body what
+        ``VEPVariantLoader.__parse_alt_alleles`` (``vep_variant_loader.py:153-213``) puts into
+        ``adsp_most_severe_consequence`` and ``adsp_ranked_consequences`` for the normalised allele.
+        Of an id two lines carry the last answers a probe.  Lines outside the device subset
+        (``counts['host_lines']``, by reason in ``counts``: DESIGN.md, K18b) are rendered by
+        :func:`annotatedvdb_amd.vep_rows.vep_rows_line` and copied into their spans after the write
+        pass; an exception it raises is re-raised with the line number attached, except
+        :class:`~annotatedvdb_amd.vep_consequences.UnrankedCombination`: such a line gives no rows
+        and is listed in ``unranked``.  On a host-only engine the library's host entries run the
+        same per-block code."""
+        return slab_passes.vep_rows_table_build(self, text, ranking)
+
+    def vep_update_rows(self, text, table: "VepRowsTable", alg_id: int, adsp: bool = False,
+                        update_existing: bool = False, contigs=None) -> "LofUpdateRows":
+        """K18b: a slab of an export ``record_primary_key<TAB>metaseq_id<TAB>vep_output[<TAB>...]``
+        (:meth:`lof_update_rows`' conventions) streamed against a :class:`VepRowsTable` ->
+        :class:`LofUpdateRows` whose rows are ``pk<TAB>chr<label><TAB>most severe<TAB>ranked<TAB>alg_id
+        [<TAB>true]<LF>`` (``true`` with ``adsp``), in export order.  A record whose ``vep_output`` is
+        not NULL is counted ``skipped`` and gets no row unless ``update_existing``
+        (``has_attribute('vep_output', ...)`` with ``skip_existing``); an id the table lacks is
+        counted ``not_annotated``; ``table.hit`` records the table rows matched."""
+        return slab_passes.vep_update_rows(self, text, table, alg_id, adsp, update_existing, contigs)
 
     # -- K17: ADSP QC pVCF update rows --------------------------------------------------
     def qc_table_build(self, text, version: str, header_fields=None) -> "QcTable":

@@ -1,7 +1,8 @@
 """The passes over a '\\n'-separated text slab behind :class:`~annotatedvdb_amd.engine.Engine`:
 K10a ``cadd_table_build``, K12 ``existing_table_build``, K13 ``cadd_update_rows``, K14
 ``export_vcf``, K15 ``split_vcf``, K16 ``lof_table_build`` / ``lof_update_rows``, K17
-``qc_table_build`` / ``qc_update_rows``, K18a ``vep_consequences`` and K19 ``txt_table_build`` /
+``qc_table_build`` / ``qc_update_rows``, K18a ``vep_consequences``, K18b ``vep_rows_table_build`` /
+``vep_update_rows`` and K19 ``txt_table_build`` /
 ``txt_update_rows`` / ``txt_direct_rows``.
 
 The two-pass ones have one shape: line count -> size pass -> its counts to the host (second
@@ -385,11 +386,13 @@ def _line_number(sp: SlabPass, offset: int) -> int:
 
 
 def _alt_table_build(engine, text, name: str, count_names, extra, host_line, all_host: bool = False,
-                     what: str = "VCF"):
+                     what: str = "VCF", row_json: bool = False):
     """The table build K16a, K17a and K19a share: entry ``avdb_<name>_size`` / ``_write`` with ``extra``
     arguments behind the line (and row) counts, one row per ALT allele of every entry (K19a: one row
     per entry), one JSON text (K19a: body) per entry; ``what`` names the file in messages.  ``host_line(line bytes, cnt)`` renders a line the device leaves to the host (flag 1 of
     its entry): ``(lookup ids, JSON, row flag bits)``.  ``all_host``: every entry is such a line.
+    ``row_json`` (K18b): a row has a JSON text of its own; ``host_line(line bytes, cnt, offset of the line)``
+    then returns one text per lookup id, and an entry's JSON is its rows' back to back.
     Returns :class:`~annotatedvdb_amd.engine.LofTable`'s members, in its order."""
     sp = SlabPass(engine, text, name, f"avdb_{name}_workspace_size")
     ent_start, ent_alts, ent_key, ent_json, ent_flags = sp.cols(torch.int64, torch.int32, torch.int32, torch.int32,
@@ -411,18 +414,20 @@ def _alt_table_build(engine, text, name: str, count_names, extra, host_line, all
     if cnt["host_lines"]:
         # the lines outside the device subset: their text to the host, rendered in file order
         host = torch.nonzero(ent_flags[:ne] & 1).flatten()
-        host_keys, host_json, host_bits = [], [], []
+        host_keys, host_json, host_bits, host_row_json = [], [], [], []
         for at, b in zip(ent_start[host].tolist(), sp.rows_bytes(ent_start[host], _lines_to_next(sp, host, ent_start, ne))):
             try:
-                keys, js, bits = host_line(b.split(b"\n", 1)[0], cnt)
+                keys, js, bits = host_line(b.split(b"\n", 1)[0], cnt, at) if row_json else \
+                    host_line(b.split(b"\n", 1)[0], cnt)
             except Exception as err:
                 err.line = _line_number(sp, at)
                 if hasattr(err, "add_note"):
                     err.add_note(f"line {err.line} of the {what}")
                 raise
             host_keys.append(keys)
-            host_json.append(js)
+            host_json.append(b"".join(js) if row_json else js)
             host_bits.append(bits)
+            host_row_json.append([len(x) for x in js] if row_json else None)
         alts = [len(k) for k in host_keys]
         kb = [sum(map(len, k)) for k in host_keys]
         cnt["rows"] += sum(alts)
@@ -447,18 +452,25 @@ def _alt_table_build(engine, text, name: str, count_names, extra, host_line, all
         koff, joff, roff = (starts(x)[host] for x in (ent_key, ent_json, ent_alts))
         sp.splice(keys, koff, [b"".join(k) for k in host_keys])
         sp.splice(json_blob, joff, host_json)
-        rows_at, offs, bits_at = [], [], []
-        for first, base, ks, bits in zip(roff.tolist(), koff.tolist(), host_keys, host_bits):
+        rows_at, offs, bits_at, joffs = [], [], [], []
+        for first, base, jbase, ks, bits, jl in zip(roff.tolist(), koff.tolist(), joff.tolist(), host_keys, host_bits,
+                                                    host_row_json):
             for a, k in enumerate(ks):
                 rows_at.append(first + a)
                 offs.append(base)
                 bits_at.append(bits)
                 base += len(k)
+                if row_json:  # a row's own span of its entry's JSON
+                    joffs.append(jbase)
+                    jbase += jl[a]
         if rows_at:
             at = torch.tensor(rows_at, dtype=torch.int64).to(engine.device)
             key_off[at] = torch.tensor(offs, dtype=torch.int64).to(engine.device)
             if any(bits_at):
                 flags[at] |= torch.tensor(bits_at, dtype=torch.uint8).to(engine.device)
+            if row_json:
+                json_off[at] = torch.tensor(joffs, dtype=torch.int64).to(engine.device)
+                json_len[at] = torch.tensor([x for jl in host_row_json for x in jl], dtype=torch.int32).to(engine.device)
     got = totals.cpu().tolist()
     if got[3] or got[:3] != [key_bytes, json_bytes, n]:
         raise N.NativeError(f"avdb_{name}_write" + sp.suffix, N.AVDB_ERANGE,
@@ -545,6 +557,63 @@ def vep_consequences(engine, text, ranking):
                             f"{got[0]} rows written, {got[1]} line(s) that differ from the size pass's {total} rows")
     return VepConsequences(engine, sp.text, ranking, sp.n_lines, cnt,
                            (n_csq, flags, types, in_start, in_len, id_start, id_len, csq_off), cols)
+
+
+def vep_rows_table_build(engine, text, ranking):
+    import json
+    import os
+    from . import bgzf
+    from .vep_consequences import ConsequenceRanking, UnrankedCombination
+    from .vep_rows import vep_rows_line
+    if not isinstance(ranking, ConsequenceRanking):
+        ranking = ConsequenceRanking(ranking)
+    if isinstance(text, (str, os.PathLike)):
+        text = bgzf.read_whole(os.fspath(text), engine)
+    text = engine._as_text(text)
+    csq = vep_consequences(engine, text, ranking)  # K18a, as it is
+    # the rank of every entry as json.dumps prints it: the device copies it, and never formats a float
+    rank_text = [json.dumps(r).encode("ascii") for r in ranking.ranks]
+    off = np.zeros(len(rank_text) + 1, dtype=np.uint32)
+    off[1:] = np.cumsum([len(t) for t in rank_text], dtype=np.uint64)
+    blob = engine._as_text(b"".join(rank_text) or b"\0")
+    rank_off = torch.from_numpy(off.view(np.int32)).to(engine.device)
+    n_total = csq.counts["consequences"]
+    el_rlen = engine.empty(max(1, n_total), torch.int32)
+    view = N.VepRowsIn(len(rank_text), n_total, N.ptr(blob), int(off[-1]), N.ptr(rank_off),
+                       *[N.ptr(getattr(csq, a)) for a in ("flags", "n_csq", "csq_off", "input_start", "input_len", "type",
+                                                          "order", "el_start", "el_len", "al_start", "al_len", "entry",
+                                                          "coding", "sorted")], N.ptr(el_rlen))
+    unranked = []
+
+    def host_line(line, cnt, at):
+        try:
+            rows = vep_rows_line(line, ranking)
+        except UnrankedCombination as err:  # the reference re-ranks here: no rows, and the line is reported
+            try:
+                vid = json.loads(line).get("id")
+            except (ValueError, AttributeError):
+                vid = None
+            unranked.append((int((text[:at] == 10).sum()) + 1, vid if isinstance(vid, str) else "", err.combination))
+            return [], [], 0
+        return ([k.encode("utf-8") for k, _, _ in rows],
+                [(ms + "\t" + ranked).encode("utf-8") for _, ms, ranked in rows], 0)
+
+    parts = _alt_table_build(engine, text, "vep_rows_table", N.VEPROWS_COUNTS, (ctypes.byref(view),), host_line,
+                             what="VEP output", row_json=True)
+    return E.VepRowsTable(*parts, ranking, unranked, (csq, blob, rank_off, el_rlen))
+
+
+def vep_update_rows(engine, text, table, alg_id: int, adsp: bool = False, update_existing: bool = False, contigs=None):
+    if table.text.device != engine.device:
+        raise ValueError("the VEP rows table lives on another device than this engine")
+    alg_id = int(alg_id)
+    if not 0 <= alg_id < 1 << 63:
+        raise ValueError("alg_id: a non-negative integer that fits 63 bits")
+    flags = (N.VEPUPD_UPDATE_EXISTING if update_existing else 0) | (N.VEPUPD_ADSP if adsp else 0)
+    n, out, row_off, match, _, cnt = _table_update_rows(
+        engine, text, table, "vep_rows_update", N.LOFUPD_COUNTS, N.LOFUPD_BAD,
+        (E.existing_contig_mask(contigs), flags, alg_id), (flags, alg_id))
+    return E.LofUpdateRows(n, out, row_off, match, cnt)
 
 
 def _copy_text(column: bytes) -> str:

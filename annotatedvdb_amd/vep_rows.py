@@ -1,0 +1,180 @@
+"""K18b: VEP results -> ``adsp_most_severe_consequence`` / ``adsp_ranked_consequences`` update rows,
+without a database — two of the four JSON columns of ``Load/bin/load_vep_result.py`` on
+``VEPVariantLoader`` (``vep_variant_loader.py:153-213``).  ``vep_output`` and ``allele_frequencies``
+are not rendered here (K18c).
+
+The reference walks VEP's ``--json`` output on one host thread: per line a ``json.loads``, a
+``VcfEntryParser`` of the top-level ``input`` string, the consequences ranked and sorted (K18a), and
+per ALT allele a ``VariantAnnotator``, a primary-key lookup by metaseq id, and
+``xstr(get_most_severe_consequence(normAlt))`` / ``xstr(get_allele_consequences(normAlt))``.  Here
+an export of the table stands in for the database, as for K16:
+
+* :meth:`Engine.vep_rows_table_build`: the JSON -> a device table of one row per ALT allele, its
+  metaseq id hashed (K6), its two columns rendered from the elements' own bytes;
+* :meth:`Engine.vep_update_rows`: the export (``record_primary_key<TAB>metaseq_id<TAB>vep_output``)
+  streamed against that table -> the update rows as text.
+
+:func:`vep_rows_line` is the reference's per-line pass in Python (the host path), :class:`VEPUpdater`
+the loader's observable surface for these columns.  ``xstr(dict)`` is taken to be ``json.dumps``
+(README, "json.dumps stand-in").  Deviations are listed in DESIGN.md (K18b).
+"""
+
+from __future__ import annotations
+
+import json
+from typing import List, Tuple
+
+from .parsers import VcfEntryParser
+from .variant_annotator import VariantAnnotator
+from .vep_consequences import TYPE_KEYS, ConsequenceRanking, most_severe_of, rank_annotation
+
+UPDATE_FIELDS = ["adsp_most_severe_consequence", "adsp_ranked_consequences", "row_algorithm_id"]
+JSONB_UPDATE_FIELDS = ["adsp_most_severe_consequence", "adsp_ranked_consequences"]
+
+
+def allele_consequences(ranked, allele):
+    """``get_allele_consequences(allele)`` over :func:`~annotatedvdb_amd.vep_consequences.vep_line`'s
+    result: ``{"<type>_consequences": [...]}`` for the types that hold the allele, or ``None``."""
+    out = {}
+    for key in TYPE_KEYS:
+        conseqs = ranked.get(key)
+        if conseqs is not None and allele in conseqs:
+            out[key] = conseqs[allele]
+    return out or None
+
+
+def _xstr_json(value) -> str:
+    return "{}" if value is None else json.dumps(value)
+
+
+def vep_rows_line(line, ranking: ConsequenceRanking) -> List[Tuple[str, str, str]]:
+    """One line (``bytes`` or ``str``) as ``parse_variant`` and ``__parse_alt_alleles`` treat it, for
+    the two consequence columns: ``[(metaseq id, adsp_most_severe_consequence,
+    adsp_ranked_consequences)]``, one per ALT allele of ``input``.  Only the first five fields of
+    ``input`` are read (``identityOnly``: INFO matters to ``allele_frequencies`` alone).  Raises what
+    the reference raises for the line: ``json.JSONDecodeError``, ``KeyError('input')``, ``IndexError``
+    (fewer than five fields), ``AttributeError`` / ``ImportError`` / ``ValueError`` / ``TypeError`` of
+    the VCF fields, what :func:`~annotatedvdb_amd.vep_consequences.vep_line` raises, and
+    :class:`~annotatedvdb_amd.vep_consequences.UnrankedCombination` where it would re-rank."""
+    annotation = json.loads(line)
+    entry = VcfEntryParser(annotation["input"], identityOnly=True)
+    variant = entry.get_variant(namespace=True)
+    ranked = rank_annotation(annotation, ranking)
+    rows = []
+    for alt in variant.alt_alleles:
+        annotator = VariantAnnotator(variant.ref_allele, alt, variant.chromosome, variant.position)
+        _, norm_alt = annotator.get_normalized_alleles(snvDivMinus=True)
+        rows.append((annotator.get_metaseq_id(), _xstr_json(most_severe_of(ranked, norm_alt)),
+                     _xstr_json(allele_consequences(ranked, norm_alt))))
+    return rows
+
+
+def update_sql(adsp: bool = False) -> str:
+    """``initialize_update_sql`` (``vep_variant_loader.py:215-247``) over this pass's fields."""
+    fields = list(UPDATE_FIELDS) + (["is_adsp_variant"] if adsp else [])
+    sets = []
+    for f in fields:
+        if f in JSONB_UPDATE_FIELDS:
+            sets.append(f"{f} = jsonb_merge(COALESCE(v.{f} ,'{{}}'::jsonb), d.{f}::jsonb)")
+        else:
+            sets.append(f"{f} = d.{f}")
+    cols = ",".join(["record_primary_key", "chromosome"] + fields)
+    return ("UPDATE AnnotatedVDB.Variant v SET " + ", ".join(sets) + " FROM (VALUES %s) AS d(" + cols + ")"
+            " WHERE v.chromosome = d.chromosome AND v.record_primary_key = d.record_primary_key")
+
+
+class VEPUpdater(object):
+    """The reference loader's observable surface for the two consequence columns, batch-wise and
+    without a database, in the mould of :class:`~annotatedvdb_amd.snpeff_lof.LOFUpdater`: counters
+    and the update buffer of ``(record_primary_key, 'chr' + c, most severe, ranked, alg id[,
+    'true'])`` tuples that ``execute_values(cursor, update_sql, buffer)`` takes.  ``table``: a
+    :class:`~annotatedvdb_amd.engine.VepRowsTable`, or the VEP output as a path (plain, gzip or
+    bgzip) or text, with ``ranking`` (a :class:`ConsequenceRanking`, or what it takes)."""
+
+    def __init__(self, table, ranking=None, alg_id: int = 0, adsp: bool = False, engine=None):
+        from .engine import VepRowsTable, default_engine
+        if engine is None:
+            engine = table.engine if isinstance(table, VepRowsTable) else default_engine()
+        self._engine = engine
+        if not isinstance(table, VepRowsTable):
+            if ranking is None:
+                raise ValueError("a ranking is needed to build the table")
+            table = engine.vep_rows_table_build(table, ranking)
+        self._table = table
+        self._alg_id, self._adsp = int(alg_id), bool(adsp)
+        self._counters = {"line": table.counts["lines"], "variant": table.n_rows, "update": 0, "duplicates": 0,
+                          "skipped": 0, "not_annotated": 0}
+        self._update_buffer: List[tuple] = []
+        self._export_rows: List[tuple] = []  # (index in _update_buffer they stand before, rows, text)
+
+    def table(self):
+        return self._table
+
+    def get_count(self, counter):
+        return self._counters[counter]
+
+    def increment_counter(self, counter):
+        self._counters[counter] += 1
+
+    def update_sql(self) -> str:
+        return update_sql(self._adsp)
+
+    def update_buffer(self, sizeOnly=False):
+        """The buffered tuples (rows from :meth:`buffer_export` are split into tuples at the first
+        call that asks for them)."""
+        if sizeOnly:
+            return len(self._update_buffer) + sum(n for _, n, _ in self._export_rows)
+        for at, _, text in reversed(self._export_rows):
+            rows = text.decode("utf-8", "surrogateescape").split("\n")[:-1]
+            self._update_buffer[at:at] = [tuple(r.split("\t")) for r in rows]
+        self._export_rows = []
+        return self._update_buffer
+
+    def update_text(self) -> bytes:
+        """The buffered rows as text, tab-separated and ``<LF>``-ended, in buffer order."""
+        parts, done = [], 0
+        for at, _, text in self._export_rows + [(len(self._update_buffer), 0, b"")]:
+            parts += [("\t".join(t) + "\n").encode("utf-8", "surrogateescape") for t in self._update_buffer[done:at]]
+            parts.append(text)
+            done = at
+        return b"".join(parts)
+
+    def reset_update_buffer(self):
+        self._update_buffer = []
+        self._export_rows = []
+
+    def buffer_export(self, path_or_text, update_existing: bool = False, contigs=None) -> int:
+        """The update rows of a whole export (:meth:`Engine.vep_update_rows`):
+        ``record_primary_key<TAB>metaseq_id<TAB>vep_output`` lines, the third column NULL as ``\\N``,
+        empty or absent, given as a path (plain, gzip or bgzip) or as text.  Moves ``update``,
+        ``skipped`` (the reference's ``duplicates``, moved as well) and ``not_annotated``; returns the
+        number of rows appended."""
+        if isinstance(path_or_text, str):
+            from . import bgzf
+            path_or_text = bgzf.read_whole(path_or_text, self._engine)
+        rows = self._engine.vep_update_rows(path_or_text, self._table, self._alg_id, adsp=self._adsp,
+                                            update_existing=update_existing, contigs=contigs)
+        for name, k in (("update", rows.n), ("skipped", rows.counts["skipped"]),
+                        ("duplicates", rows.counts["skipped"]), ("not_annotated", rows.counts["not_annotated"])):
+            self._counters[name] += k
+        if rows.n:
+            self._export_rows.append((len(self._update_buffer), rows.n, rows.text.cpu().numpy().tobytes()))
+        return rows.n
+
+    def unmatched(self) -> List[str]:
+        """The metaseq ids of the table no export row has matched so far, in file order (an id two
+        lines carry once; its last line is the one that answers)."""
+        t = self._table
+        if t.n_rows == 0:
+            return []
+        hit = t.hit.cpu().numpy()
+        off = t.key_off.cpu().numpy()
+        blob = t.keys.cpu().numpy().tobytes()
+        last = {}
+        for r in range(t.n_rows):
+            last[blob[off[r]:off[r + 1]]] = r
+        return [k.decode("utf-8", "surrogateescape") for k, r in last.items() if not hit[r]]
+
+    def unranked(self) -> List[tuple]:
+        """The lines that need a re-rank and gave no rows: ``(line number, id, combination)``."""
+        return list(self._table.unranked)

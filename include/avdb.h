@@ -1653,6 +1653,125 @@ int avdb_vep_index_write_host(const avdb_ctx* ctx, const uint8_t* text, size_t t
                               uint64_t* mask, int32_t* entry, uint8_t* coding, int32_t* sorted, uint8_t* head,
                               uint64_t* totals);
 
+/* ---- K18b: VEP consequence update rows (Load/bin/load_vep_result.py, two of its four columns) ----
+ * The update rows for adsp_most_severe_consequence and adsp_ranked_consequences of VEPVariantLoader
+ * (vep_variant_loader.py:153-213), on K18a's arrays of the same slab and K16's two-half shape.
+ * Table build: every line is an entry.  A line the device answers gives one row per ALT allele of
+ * the VCF line in its top-level `input` string (its first five fields, separated by the two bytes
+ * \t): the row's key is the metaseq id chrom:pos:ref:alt (CHROM without 'chr', MT as M, POS without
+ * leading zeros), its body <most severe><TAB><ranked>: json.dumps of get_most_severe_consequence
+ * (normAlt) and of get_allele_consequences(normAlt), '{}' for None, normAlt the ALT without the
+ * prefix it shares with REF ('-' when nothing is left; an SNV as it is).  An element is rendered
+ * from its own bytes: a space behind every ',' and ':' outside strings, and
+ * `, "vep_consequence_order_num": k, "rank": r, "consequence_is_coding": true|false` before its
+ * closing brace; r is entry e's text rank_text[rank_off[e] .. rank_off[e + 1]).  A line outside the
+ * device subset is flagged AVDB_VEPROWS_LINE_HOST (no rows, keys or body counted; the caller
+ * patches ent_alts, ent_key_bytes and ent_json_len and copies its bytes in after the write pass):
+ * K18a's reasons 0 .. 10, then 11 no `input` string, 12 `input` with fewer than five fields, a
+ * backslash other than the separators' or a field outside K16's first-five-field subset, 13 a
+ * backslash escape other than \" \\ \b \f \n \r \t in an element, 14 a byte >= 0x80 or < 0x20 in
+ * an element, 15 a token outside strings that is not true, false, null, an integer without a
+ * leading zero (not -0), or -?int.frac of at most 15 significant digits without a trailing zero
+ * (a fraction of exactly 0 excepted) and of magnitude in [1e-4, 1e16), of at most 32 bytes.  The
+ * first reason r is counted under AVDB_VEPROWS_COUNT_REASON0 + r and kept in the entry's flags as
+ * (r + 1) << 2.
+ *   1. avdb_vep_rows_table_size: el_rlen[c] for every consequence of a line K18a answered (its
+ *      rendered length, or 0x80000000 | reason), then per entry its columns as avdb_lof_table_size.
+ *   2. avdb_vep_rows_table_write: as avdb_lof_table_write; a row's json_off / json_len is its own
+ *      body, an entry's ent_json_len their sum.
+ * Export join (avdb_vep_rows_update_size / _write): avdb_lof_update_size's export, table view,
+ * counts (AVDB_LOFUPD_COUNT_*), row flags and conventions, the third column being vep_output; a
+ * row is pk<TAB>chr<label><TAB>body<TAB>alg_id[<TAB>true]<LF>, `true` with AVDB_VEPUPD_ADSP. */
+#define AVDB_VEPROWS_LINE_HOST 0x01u
+#define AVDB_VEPROWS_LINE_BAD 0x02u /* (no line is) */
+#define AVDB_VEPROWS_ROW_FIRST 0x04u
+#define AVDB_VEPROWS_N_REASONS 16
+#define AVDB_VEPROWS_MAX_TOKEN 32
+#define AVDB_VEPROWS_COUNT_ROWS 0
+#define AVDB_VEPROWS_COUNT_LINES 1
+#define AVDB_VEPROWS_COUNT_HOST_LINES 2
+#define AVDB_VEPROWS_COUNT_BAD 3
+#define AVDB_VEPROWS_COUNT_KEY_BYTES 4
+#define AVDB_VEPROWS_COUNT_JSON_BYTES 5
+#define AVDB_VEPROWS_COUNT_LONE_CR 6 /* always 0: K18a drops a line's last '\r', any other sends the line to the host */
+#define AVDB_VEPROWS_COUNT_ENTRIES 7
+#define AVDB_VEPROWS_COUNT_REASON0 8
+#define AVDB_VEPROWS_N_COUNTS 24
+#define AVDB_VEPUPD_UPDATE_EXISTING 0x01u /* avdb_vep_rows_update_size's flags */
+#define AVDB_VEPUPD_ADSP 0x02u            /* ... and avdb_vep_rows_update_write's */
+typedef struct avdb_vep_rows_in {
+  uint32_t struct_size; /* sizeof(avdb_vep_rows_in) */
+  uint32_t n_ranks;     /* the ranking's entries */
+  uint64_t n_csq_total;
+  const uint8_t* rank_text;
+  uint64_t rank_text_bytes;
+  const uint32_t* rank_off; /* n_ranks + 1 */
+  /* per line, as avdb_vep_index_size left them (csq_off: the caller's sums) */
+  const uint8_t* line_flags;
+  const uint32_t* n_csq;
+  const uint64_t* csq_off;
+  const uint64_t* input_start;
+  const int32_t* input_len;
+  /* per consequence, as avdb_vep_index_write left them */
+  const uint8_t* type;
+  const int32_t* order;
+  const uint64_t* el_start;
+  const uint32_t* el_len;
+  const uint64_t* al_start;
+  const uint32_t* al_len;
+  const int32_t* entry;
+  const uint8_t* coding;
+  const int32_t* sorted;
+  uint32_t* el_rlen; /* per consequence: written by the size entry, read by the write entry */
+} avdb_vep_rows_in;
+typedef avdb_lof_table avdb_vep_rows_table;
+int avdb_vep_rows_table_workspace_size(size_t text_bytes, size_t n_lines, size_t* bytes);
+int avdb_vep_rows_table_size(avdb_ctx* ctx, const uint8_t* text, size_t text_bytes, size_t n_lines,
+                             const avdb_vep_rows_in* in, uint64_t* ent_start, uint32_t* ent_alts,
+                             uint32_t* ent_key_bytes, uint32_t* ent_json_len, uint8_t* ent_flags, uint64_t* counts,
+                             void* workspace, size_t workspace_bytes, void* stream);
+int avdb_vep_rows_table_write(avdb_ctx* ctx, const uint8_t* text, size_t text_bytes, size_t n_lines, size_t n_entries,
+                              size_t n_rows, const avdb_vep_rows_in* in, const uint64_t* ent_start,
+                              const uint32_t* ent_alts, const uint32_t* ent_key_bytes, const uint32_t* ent_json_len,
+                              const uint8_t* ent_flags, uint8_t* keys, size_t key_cap, uint64_t* key_off, uint8_t* json,
+                              size_t json_cap, uint64_t* row_json_off, uint32_t* row_json_len, uint64_t* row_line_start,
+                              uint8_t* row_flags, uint64_t* totals, void* workspace, size_t workspace_bytes,
+                              void* stream);
+int avdb_vep_rows_table_size_host(const avdb_ctx* ctx, const uint8_t* text, size_t text_bytes, size_t n_lines,
+                                  const avdb_vep_rows_in* in, uint64_t* ent_start, uint32_t* ent_alts,
+                                  uint32_t* ent_key_bytes, uint32_t* ent_json_len, uint8_t* ent_flags,
+                                  uint64_t* counts);
+int avdb_vep_rows_table_write_host(const avdb_ctx* ctx, const uint8_t* text, size_t text_bytes, size_t n_lines,
+                                   size_t n_entries, size_t n_rows, const avdb_vep_rows_in* in,
+                                   const uint64_t* ent_start, const uint32_t* ent_alts, const uint32_t* ent_key_bytes,
+                                   const uint32_t* ent_json_len, const uint8_t* ent_flags, uint8_t* keys,
+                                   size_t key_cap, uint64_t* key_off, uint8_t* json, size_t json_cap,
+                                   uint64_t* row_json_off, uint32_t* row_json_len, uint64_t* row_line_start,
+                                   uint8_t* row_flags, uint64_t* totals);
+/* 1 when the n bytes are a token the device copies (reason 15's rule), else 0 */
+int avdb_vep_rows_token_ok_host(const uint8_t* token, size_t n);
+int avdb_vep_rows_update_workspace_size(size_t text_bytes, size_t n_lines, size_t* bytes);
+int avdb_vep_rows_update_size(avdb_ctx* ctx, const uint8_t* text, size_t text_bytes, size_t n_lines,
+                              const avdb_vep_rows_table* table, uint32_t contig_mask, uint32_t flags, uint64_t alg_id,
+                              uint64_t* row_start, uint32_t* pk_len, int32_t* match, uint32_t* out_len,
+                              uint8_t* row_flags, uint64_t* counts, void* workspace, size_t workspace_bytes,
+                              void* stream);
+int avdb_vep_rows_update_write(avdb_ctx* ctx, const uint8_t* text, size_t text_bytes, size_t n_lines, size_t n_rows,
+                               const avdb_vep_rows_table* table, uint32_t flags, uint64_t alg_id,
+                               const uint64_t* row_start, const uint32_t* pk_len, const int32_t* match,
+                               const uint32_t* out_len, const uint8_t* row_flags, uint8_t* out, size_t out_cap,
+                               uint64_t* row_off, uint64_t* totals, void* workspace, size_t workspace_bytes,
+                               void* stream);
+int avdb_vep_rows_update_size_host(const avdb_ctx* ctx, const uint8_t* text, size_t text_bytes, size_t n_lines,
+                                   const avdb_vep_rows_table* table, uint32_t contig_mask, uint32_t flags,
+                                   uint64_t alg_id, uint64_t* row_start, uint32_t* pk_len, int32_t* match,
+                                   uint32_t* out_len, uint8_t* row_flags, uint64_t* counts);
+int avdb_vep_rows_update_write_host(const avdb_ctx* ctx, const uint8_t* text, size_t text_bytes, size_t n_lines,
+                                    size_t n_rows, const avdb_vep_rows_table* table, uint32_t flags, uint64_t alg_id,
+                                    const uint64_t* row_start, const uint32_t* pk_len, const int32_t* match,
+                                    const uint32_t* out_len, const uint8_t* row_flags, uint8_t* out, size_t out_cap,
+                                    uint64_t* row_off, uint64_t* totals);
+
 /* ---- host-side formatting of kernel outputs -------------------------------
  * ltree path text (<= AVDB_MAX_PATH bytes).  Returns the length written (no
  * NUL terminator counted; one is written if cap allows), or a negative code. */
