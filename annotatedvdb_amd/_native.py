@@ -119,6 +119,11 @@ VEPROWS_COUNTS = ("rows", "lines", "host_lines", "bad", "key_bytes", "json_bytes
                   "entries") + VEPROWS_REASONS  # AVDB_VEPROWS_COUNT_*, by slot
 VEPROWS_N_COUNTS = len(VEPROWS_COUNTS)
 VEPUPD_UPDATE_EXISTING, VEPUPD_ADSP = 1, 2  # AVDB_VEPUPD_* (the join's counts and row flags are K16b's: LOFUPD_*)
+VEPOUT_IDENTITY_ONLY = 1  # AVDB_VEPOUT_IDENTITY_ONLY
+VEPOUT_REASONS = VEPROWS_REASONS + ("kept_text", "eight_fields",
+                                    "input_value")  # why a line's cleaned text is the host's, by flags - 1
+VEPOUT_COUNTS = ("lines", "host_lines", "out_bytes") + VEPOUT_REASONS  # AVDB_VEPOUT_COUNT_*, by slot
+VEPOUT_N_COUNTS = len(VEPOUT_COUNTS)
 EXPVCF_ROW_HOST, EXPVCF_BAD, EXPVCF_DROPPED = 1, 2, 4  # AVDB_EXPVCF_* row flags
 EXPVCF_STREAM_VCF, EXPVCF_STREAM_INVALID = 0, 1
 EXPVCF_COUNTS = ("valid", "invalid", "skipped_lines", "filtered", "bad", "lone_cr", "vcf_bytes",
@@ -235,6 +240,16 @@ class VepRowsIn(ctypes.Structure):
         super().__init__(ctypes.sizeof(VepRowsIn), n_ranks, n_csq_total, rank_text, rank_text_bytes, rank_off, *arrays)
 
 
+class VepOutputTable(ctypes.Structure):
+    """avdb_vep_output_table (include/avdb.h); ``struct_size`` is filled in."""
+    _fields_ = [("struct_size", ctypes.c_uint32), ("reserved", ctypes.c_uint32), ("n_entries", ctypes.c_uint64),
+                ("text", ctypes.c_void_p), ("text_bytes", ctypes.c_uint64), ("off", ctypes.c_void_p),
+                ("len", ctypes.c_void_p), ("row_entry", ctypes.c_void_p)]
+
+    def __init__(self, n_entries: int = 0, text=None, text_bytes: int = 0, off=None, length=None, row_entry=None):
+        super().__init__(ctypes.sizeof(VepOutputTable), 0, n_entries, text, text_bytes, off, length, row_entry)
+
+
 class LineResult(ctypes.Structure):
     """avdb_line_result (include/avdb.h)."""
     _fields_ = [(name, ctypes.c_uint32) for name in ("state", "flags", "copy_bytes", "map_bytes", "n_rec", "n_rows",
@@ -297,6 +312,9 @@ EXPORTED_SYMBOLS = [
     "avdb_vep_rows_table_size_host", "avdb_vep_rows_table_write_host", "avdb_vep_rows_token_ok_host",
     "avdb_vep_rows_update_workspace_size", "avdb_vep_rows_update_size", "avdb_vep_rows_update_write",
     "avdb_vep_rows_update_size_host", "avdb_vep_rows_update_write_host",
+    "avdb_vep_output_workspace_size", "avdb_vep_output_size", "avdb_vep_output_write",
+    "avdb_vep_output_size_host", "avdb_vep_output_write_host",
+    "avdb_vep_output_update_write", "avdb_vep_output_update_write_host",
 ]
 
 
@@ -510,6 +528,14 @@ def _sig(lib):
     f.avdb_vep_rows_update_size.argtypes = f.avdb_vep_rows_update_size_host.argtypes + [P, SZ, P]
     f.avdb_vep_rows_update_write_host.argtypes = [P, P, SZ, SZ, SZ, LT, U32, ctypes.c_uint64, P, P, P, P, P, P, SZ, P, P]
     f.avdb_vep_rows_update_write.argtypes = f.avdb_vep_rows_update_write_host.argtypes + [P, SZ, P]
+    f.avdb_vep_output_workspace_size.argtypes = [SZ, SZ, ctypes.POINTER(SZ)]
+    f.avdb_vep_output_size_host.argtypes = [P, P, SZ, SZ, VR, P, U32] + [P] * 6
+    f.avdb_vep_output_size.argtypes = f.avdb_vep_output_size_host.argtypes + [P, SZ, P]
+    f.avdb_vep_output_write_host.argtypes = [P, P, SZ, SZ, VR, U32, P, P, P, P, P, P, SZ, P]
+    f.avdb_vep_output_write.argtypes = f.avdb_vep_output_write_host.argtypes + [P, SZ, P]
+    f.avdb_vep_output_update_write_host.argtypes = [P, P, SZ, SZ, SZ, LT, ctypes.POINTER(VepOutputTable), U32,
+                                                    ctypes.c_uint64, P, P, P, P, P, P, SZ, P, P]
+    f.avdb_vep_output_update_write.argtypes = f.avdb_vep_output_update_write_host.argtypes + [P, SZ, P]
     for name in EXPORTED_SYMBOLS:
         if name not in ("avdb_last_error",):
             getattr(f, name).restype = I32

@@ -190,10 +190,27 @@ class VepRowsTable(LofTable):
     ``<adsp_most_severe_consequence><TAB><adsp_ranked_consequences>`` as ``json.dumps`` prints them
     (``{}`` for ``None``); ``counts`` by ``N.VEPROWS_COUNTS``; ``ranking`` the
     :class:`~annotatedvdb_amd.vep_consequences.ConsequenceRanking`; ``unranked`` the lines that need a
-    re-rank and gave no rows, ``(line number, id, combination)``."""
+    re-rank and gave no rows, ``(line number, id, combination)``.  Built with ``vep_output=True``
+    (K18c) it also holds every line's cleaned result once: entry (line) ``e``'s text is
+    ``cleaned[cleaned_off[e]:cleaned_off[e] + cleaned_len[e]]``, ``row_entry[k]`` the entry of row
+    ``k`` (the rows of a multi-allelic line share one text), ``cleaned_flags[e]`` 0 or 1 + the reason
+    the host rendered it (``N.VEPOUT_REASONS``), ``cleaned_counts`` by ``N.VEPOUT_COUNTS``,
+    ``identity_only`` the form of ``input``'s dict; else these are ``None``."""
     ranking: object = None
     unranked: list = None
     _keep: tuple = ()  # K18a's arrays and the rank text, which the table's build read
+    cleaned: torch.Tensor = None
+    cleaned_off: torch.Tensor = None
+    cleaned_len: torch.Tensor = None
+    row_entry: torch.Tensor = None
+    cleaned_flags: torch.Tensor = None
+    cleaned_counts: Dict[str, int] = None
+    identity_only: bool = False
+
+    def cleaned_view(self) -> "N.VepOutputTable":
+        """The C struct over the cleaned texts (valid while the tensors are alive)."""
+        return N.VepOutputTable(self.cleaned_off.numel(), N.ptr(self.cleaned), self.cleaned.numel(),
+                                N.ptr(self.cleaned_off), N.ptr(self.cleaned_len), N.ptr(self.row_entry))
 
 
 @dataclass
@@ -1693,7 +1710,8 @@ class Engine:
         return slab_passes.vep_consequences(self, text, ranking)
 
     # -- K18b: VEP consequence update rows ------------------------------------------------
-    def vep_rows_table_build(self, text, ranking) -> "VepRowsTable":
+    def vep_rows_table_build(self, text, ranking, vep_output: bool = False,
+                             identity_only: bool = False) -> "VepRowsTable":
         """K18b: VEP ``--json`` output (what :meth:`vep_consequences` takes) and a ranking ->
         :class:`VepRowsTable` on this engine's device: K18a's pass, then one row per ALT allele of the
         VCF line in every line's ``input``, keyed by its metaseq id ``chrom:pos:ref:alt``, its body what
@@ -1705,8 +1723,16 @@ class Engine:
         pass; an exception it raises is re-raised with the line number attached, except
         :class:`~annotatedvdb_amd.vep_consequences.UnrankedCombination`: such a line gives no rows
         and is listed in ``unranked``.  On a host-only engine the library's host entries run the
-        same per-block code."""
-        return slab_passes.vep_rows_table_build(self, text, ranking)
+        same per-block code.
+
+        ``vep_output=True`` (K18c) adds the cleaned result of every line, stored once per line:
+        ``xstr(cleanResult)`` of ``__clean_result`` (``vep_variant_loader.py:112-123``), the line's
+        object without ``colocated_variants`` and the four ``<type>_consequences`` members and with
+        ``VcfEntryParser(input, identityOnly=identity_only).get_entry()`` in place of ``input``.  A
+        line outside that pass's device subset (``cleaned_counts``) is rendered by
+        :func:`annotatedvdb_amd.vep_rows.vep_output_line`.  With ``vep_output=False`` the table is
+        K18b's, byte for byte."""
+        return slab_passes.vep_rows_table_build(self, text, ranking, vep_output, identity_only)
 
     def vep_update_rows(self, text, table: "VepRowsTable", alg_id: int, adsp: bool = False,
                         update_existing: bool = False, contigs=None) -> "LofUpdateRows":
@@ -1716,7 +1742,9 @@ class Engine:
         [<TAB>true]<LF>`` (``true`` with ``adsp``), in export order.  A record whose ``vep_output`` is
         not NULL is counted ``skipped`` and gets no row unless ``update_existing``
         (``has_attribute('vep_output', ...)`` with ``skip_existing``); an id the table lacks is
-        counted ``not_annotated``; ``table.hit`` records the table rows matched."""
+        counted ``not_annotated``; ``table.hit`` records the table rows matched.  A table built with
+        ``vep_output=True`` (K18c) gives ``...<TAB>ranked<TAB>vep_output<TAB>alg_id...`` rows, written
+        one wave per row."""
         return slab_passes.vep_update_rows(self, text, table, alg_id, adsp, update_existing, contigs)
 
     # -- K17: ADSP QC pVCF update rows --------------------------------------------------

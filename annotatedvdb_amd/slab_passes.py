@@ -2,7 +2,7 @@
 K10a ``cadd_table_build``, K12 ``existing_table_build``, K13 ``cadd_update_rows``, K14
 ``export_vcf``, K15 ``split_vcf``, K16 ``lof_table_build`` / ``lof_update_rows``, K17
 ``qc_table_build`` / ``qc_update_rows``, K18a ``vep_consequences``, K18b ``vep_rows_table_build`` /
-``vep_update_rows`` and K19 ``txt_table_build`` /
+``vep_update_rows`` (with K18c's ``vep_output`` column on request) and K19 ``txt_table_build`` /
 ``txt_update_rows`` / ``txt_direct_rows``.
 
 The two-pass ones have one shape: line count -> size pass -> its counts to the host (second
@@ -386,13 +386,14 @@ def _line_number(sp: SlabPass, offset: int) -> int:
 
 
 def _alt_table_build(engine, text, name: str, count_names, extra, host_line, all_host: bool = False,
-                     what: str = "VCF", row_json: bool = False):
+                     what: str = "VCF", row_json: bool = False, keep=None):
     """The table build K16a, K17a and K19a share: entry ``avdb_<name>_size`` / ``_write`` with ``extra``
     arguments behind the line (and row) counts, one row per ALT allele of every entry (K19a: one row
     per entry), one JSON text (K19a: body) per entry; ``what`` names the file in messages.  ``host_line(line bytes, cnt)`` renders a line the device leaves to the host (flag 1 of
     its entry): ``(lookup ids, JSON, row flag bits)``.  ``all_host``: every entry is such a line.
     ``row_json`` (K18b): a row has a JSON text of its own; ``host_line(line bytes, cnt, offset of the line)``
-    then returns one text per lookup id, and an entry's JSON is its rows' back to back.
+    then returns one text per lookup id, and an entry's JSON is its rows' back to back.  ``keep`` (K18c): a dict
+    that receives the entries' columns as ``keep["ents"]`` and their number as ``keep["n_entries"]``.
     Returns :class:`~annotatedvdb_amd.engine.LofTable`'s members, in its order."""
     sp = SlabPass(engine, text, name, f"avdb_{name}_workspace_size")
     ent_start, ent_alts, ent_key, ent_json, ent_flags = sp.cols(torch.int64, torch.int32, torch.int32, torch.int32,
@@ -405,6 +406,8 @@ def _alt_table_build(engine, text, name: str, count_names, extra, host_line, all
         raise ValueError(f"{cnt['lone_cr']} carriage return(s) inside lines of the {what}: Python's text mode ends a "
                          "line there and the device pass does not")
     ne = cnt["entries"]
+    if keep is not None:
+        keep.update(ents=ents, n_entries=ne)
     if all_host and ne:
         ent_flags[:ne] |= 1
         for col in (ent_alts, ent_key, ent_json):
@@ -559,7 +562,60 @@ def vep_consequences(engine, text, ranking):
                            (n_csq, flags, types, in_start, in_len, id_start, id_len, csq_off), cols)
 
 
-def vep_rows_table_build(engine, text, ranking):
+def _vep_cleaned(engine, text, view, ent_flags, row_line_start, identity_only: bool):
+    """K18c: the cleaned result of every line of the slab K18b's table was built from, once per line: the size
+    pass, the lines it leaves to the host rendered by :func:`~annotatedvdb_amd.vep_rows.vep_output_line`, the
+    offsets, the write pass, the host texts copied into their spans.  ``view``: K18b's ``VepRowsIn``;
+    ``ent_flags``: its entries' flags (entry e is line e); ``row_line_start``: the table rows' line starts.
+    Returns ``(blob, off, len, row_entry, flags, counts)``."""
+    from .vep_rows import vep_output_line
+    sp = SlabPass(engine, text, "vep_output", "avdb_vep_output_workspace_size")
+    nl = sp.n_lines
+    line_start, out_len, dict_at, dict_len, flags = sp.cols(torch.int64, torch.int32, torch.int32, torch.int32,
+                                                            torch.uint8)
+    counts = engine.empty(N.VEPOUT_N_COUNTS, torch.int64)
+    fl = N.VEPOUT_IDENTITY_ONLY if identity_only else 0
+    vp = ctypes.byref(view)
+    sp.call("avdb_vep_output_size", sp.tp, sp.nb, nl, vp, ent_flags, fl, line_start, out_len, dict_at, dict_len, flags,
+            counts)
+    cnt = sp.counts(counts, N.VEPOUT_COUNTS)
+    device_bytes = cnt["out_bytes"]
+    host, rendered = None, []
+    if cnt["host_lines"]:
+        host = torch.nonzero(flags[:nl]).flatten()
+        for at, b in zip(line_start[host].tolist(),
+                         sp.rows_bytes(line_start[host], _lines_to_next(sp, host, line_start, nl))):
+            try:
+                rendered.append(vep_output_line(b.split(b"\n", 1)[0], identity_only).encode("utf-8"))
+            except Exception as err:
+                err.line = _line_number(sp, at)
+                err.counts = cnt  # (the size pass's counts by reason: what sent the line here)
+                if hasattr(err, "add_note"):
+                    err.add_note(f"line {err.line} of the VEP output")
+                raise
+        out_len[host] = sp.lengths(rendered).to(torch.int32)
+        cnt["out_bytes"] += sum(map(len, rendered))
+    total = cnt["out_bytes"]
+    lens = out_len[:nl].long()
+    off = torch.zeros(sp.m, dtype=torch.int64, device=engine.device)
+    off[:nl] = torch.cumsum(lens, 0) - lens
+    blob = engine.empty(max(1, total), torch.uint8)
+    totals = engine.empty(2, torch.int64)
+    sp.call("avdb_vep_output_write", sp.tp, sp.nb, nl, vp, fl, off, out_len, dict_at, dict_len, flags, blob, total, totals)
+    if host is not None and host.numel():
+        sp.splice(blob, off[host], rendered)
+    got = totals.cpu().tolist()
+    if got != [device_bytes, 0]:
+        raise N.NativeError("avdb_vep_output_write" + sp.suffix, N.AVDB_ERANGE,
+                            f"{got[0]} bytes written, {got[1]} line(s) that differ from the size pass's {device_bytes} bytes")
+    if nl and row_line_start.numel():
+        row_entry = (torch.searchsorted(line_start[:nl].contiguous(), row_line_start.contiguous(), right=True) - 1).to(torch.int32)
+    else:
+        row_entry = torch.zeros(max(1, row_line_start.numel()), dtype=torch.int32, device=engine.device)
+    return blob[:total], off[:nl], out_len[:nl], row_entry, flags[:nl], cnt
+
+
+def vep_rows_table_build(engine, text, ranking, vep_output: bool = False, identity_only: bool = False):
     import json
     import os
     from . import bgzf
@@ -598,9 +654,15 @@ def vep_rows_table_build(engine, text, ranking):
         return ([k.encode("utf-8") for k, _, _ in rows],
                 [(ms + "\t" + ranked).encode("utf-8") for _, ms, ranked in rows], 0)
 
+    kept = {} if vep_output else None
     parts = _alt_table_build(engine, text, "vep_rows_table", N.VEPROWS_COUNTS, (ctypes.byref(view),), host_line,
-                             what="VEP output", row_json=True)
-    return E.VepRowsTable(*parts, ranking, unranked, (csq, blob, rank_off, el_rlen))
+                             what="VEP output", row_json=True, keep=kept)
+    table = E.VepRowsTable(*parts, ranking, unranked, (csq, blob, rank_off, el_rlen))
+    if vep_output:
+        (table.cleaned, table.cleaned_off, table.cleaned_len, table.row_entry, table.cleaned_flags,
+         table.cleaned_counts) = _vep_cleaned(engine, text, view, kept["ents"][4], table.line_start, identity_only)
+        table.identity_only = bool(identity_only)
+    return table
 
 
 def vep_update_rows(engine, text, table, alg_id: int, adsp: bool = False, update_existing: bool = False, contigs=None):
@@ -610,9 +672,21 @@ def vep_update_rows(engine, text, table, alg_id: int, adsp: bool = False, update
     if not 0 <= alg_id < 1 << 63:
         raise ValueError("alg_id: a non-negative integer that fits 63 bits")
     flags = (N.VEPUPD_UPDATE_EXISTING if update_existing else 0) | (N.VEPUPD_ADSP if adsp else 0)
+    widen = write_name = None
+    write_extra = (flags, alg_id)
+    if table.cleaned is not None:  # K18c: the row grows by <TAB> and its line's cleaned text
+        cleaned = table.cleaned_view()
+        write_name, write_extra = "avdb_vep_output_update_write", (ctypes.byref(cleaned), flags, alg_id)
+
+        def widen(sp, row_start, out_len, row_flags, match, n, cnt):
+            if n:
+                add = 1 + table.cleaned_len[table.row_entry[match[:n].long()].long()]
+                out_len[:n] += add
+                cnt["out_bytes"] += int(add.sum())
+
     n, out, row_off, match, _, cnt = _table_update_rows(
         engine, text, table, "vep_rows_update", N.LOFUPD_COUNTS, N.LOFUPD_BAD,
-        (E.existing_contig_mask(contigs), flags, alg_id), (flags, alg_id))
+        (E.existing_contig_mask(contigs), flags, alg_id), write_extra, widen=widen, write_name=write_name)
     return E.LofUpdateRows(n, out, row_off, match, cnt)
 
 
@@ -631,11 +705,14 @@ def _copy_text(column: bytes) -> str:
 
 
 def _table_update_rows(engine, text, table, name: str, count_names, bad_bit: int, size_extra, write_extra,
-                       fix_host_rows=None):
+                       fix_host_rows=None, widen=None, write_name=None):
     """The export join K16b, K17b and K19b share: entry ``avdb_<name>_size`` / ``_write`` with ``size_extra`` and
     ``write_extra`` arguments behind the table view, one row per record of the export whose id the table holds.
     ``fix_host_rows(sp, row_start, out_len, flags, n, cnt)`` settles the rows the device left to the host between
     the passes and returns how many of them it dropped (their ``out_len`` zeroed, ``cnt`` brought up to date).
+    ``widen(sp, row_start, out_len, flags, match, n, cnt)`` (K18c) adds to the rows' lengths what ``write_name``, the
+    write entry in place of ``avdb_<name>_write``, puts into them beyond the size entry's row; it shares the size
+    entry's workspace.
     Returns ``(rows kept, text, row_off, match, flags, cnt)``."""
     view = table.view()
     vp = ctypes.byref(view)
@@ -651,13 +728,16 @@ def _table_update_rows(engine, text, table, name: str, count_names, bad_bit: int
     if cnt["bad"]:
         sp.raise_bad_metaseq(row_start, flags, bad_bit, n, cnt["bad"])
     dropped = fix_host_rows(sp, row_start, out_len, flags, n, cnt) if fix_host_rows and cnt["host_rows"] else 0
+    if widen is not None:
+        widen(sp, row_start, out_len, flags, match, n, cnt)
+    write_name = write_name or f"avdb_{name}_write"
     out_bytes = cnt["out_bytes"]
     out_text = engine.empty(max(1, out_bytes), torch.uint8)
     row_off = engine.empty(n + 1, torch.int64)
     totals = engine.empty(2, torch.int64)
-    sp.call(f"avdb_{name}_write", sp.tp, sp.nb, sp.n_lines, n, vp, *write_extra, row_start, pk_len, match, out_len, flags,
+    sp.call(write_name, sp.tp, sp.nb, sp.n_lines, n, vp, *write_extra, row_start, pk_len, match, out_len, flags,
             out_text, out_bytes, row_off, totals)
-    sp.check_totals(f"avdb_{name}_write", totals.cpu().tolist(), out_bytes, "rows")
+    sp.check_totals(write_name, totals.cpu().tolist(), out_bytes, "rows")
     return n - dropped, out_text[:out_bytes], row_off, match[:n], flags[:n], cnt
 
 

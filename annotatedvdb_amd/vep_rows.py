@@ -1,7 +1,8 @@
 """K18b: VEP results -> ``adsp_most_severe_consequence`` / ``adsp_ranked_consequences`` update rows,
 without a database — two of the four JSON columns of ``Load/bin/load_vep_result.py`` on
-``VEPVariantLoader`` (``vep_variant_loader.py:153-213``).  ``vep_output`` and ``allele_frequencies``
-are not rendered here (K18c).
+``VEPVariantLoader`` (``vep_variant_loader.py:153-213``), and on request a third, ``vep_output`` (K18c:
+the cleaned result, :func:`vep_output_line`).  ``allele_frequencies`` is not rendered here (K18d,
+DESIGN.md §7).
 
 The reference walks VEP's ``--json`` output on one host thread: per line a ``json.loads``, a
 ``VcfEntryParser`` of the top-level ``input`` string, the consequences ranked and sorted (K18a), and
@@ -69,12 +70,33 @@ def vep_rows_line(line, ranking: ConsequenceRanking) -> List[Tuple[str, str, str
     return rows
 
 
-def update_sql(adsp: bool = False) -> str:
-    """``initialize_update_sql`` (``vep_variant_loader.py:215-247``) over this pass's fields."""
-    fields = list(UPDATE_FIELDS) + (["is_adsp_variant"] if adsp else [])
+def vep_output_line(line, identity_only: bool = False) -> str:
+    """K18c's host path: ``xstr(cleanResult)`` of one line (``bytes`` or ``str``), the same text for every
+    ALT allele.  ``parse_variant`` (``vep_variant_loader.py:262-296``) puts ``VcfEntryParser(input,
+    identityOnly).get_entry()`` in place of the ``input`` string, ``__clean_result`` (``:112-123``) pops
+    ``colocated_variants`` and the four ``<type>_consequences`` keys, and ``xstr(dict)`` is taken to be
+    ``json.dumps``.  Raises what the reference raises before it: ``json.JSONDecodeError``,
+    ``KeyError('input')``, ``IndexError`` (fewer fields than ``identity_only`` asks for: five, else eight),
+    ``ImportError`` (an INFO that is a number)."""
+    annotation = json.loads(line)
+    entry = VcfEntryParser(annotation["input"], identityOnly=identity_only)
+    annotation["input"] = entry.get_entry()
+    annotation.pop("colocated_variants", None)
+    for key in TYPE_KEYS:
+        annotation.pop(key, None)
+    return json.dumps(annotation)
+
+
+def update_sql(adsp: bool = False, vep_output: bool = False) -> str:
+    """``initialize_update_sql`` (``vep_variant_loader.py:215-247``) over this pass's fields;
+    ``vep_output``: the cleaned result's column too, before ``row_algorithm_id`` as in ``COPY_FIELDS``."""
+    fields = list(UPDATE_FIELDS)
+    if vep_output:
+        fields.insert(fields.index("row_algorithm_id"), "vep_output")
+    fields += ["is_adsp_variant"] if adsp else []
     sets = []
     for f in fields:
-        if f in JSONB_UPDATE_FIELDS:
+        if f in JSONB_UPDATE_FIELDS or f == "vep_output":
             sets.append(f"{f} = jsonb_merge(COALESCE(v.{f} ,'{{}}'::jsonb), d.{f}::jsonb)")
         else:
             sets.append(f"{f} = d.{f}")
@@ -86,12 +108,14 @@ def update_sql(adsp: bool = False) -> str:
 class VEPUpdater(object):
     """The reference loader's observable surface for the two consequence columns, batch-wise and
     without a database, in the mould of :class:`~annotatedvdb_amd.snpeff_lof.LOFUpdater`: counters
-    and the update buffer of ``(record_primary_key, 'chr' + c, most severe, ranked, alg id[,
-    'true'])`` tuples that ``execute_values(cursor, update_sql, buffer)`` takes.  ``table``: a
+    and the update buffer of ``(record_primary_key, 'chr' + c, most severe, ranked[, vep_output], alg id[,
+    'true'])`` tuples (``vep_output``: K18c's column, the table built with it; ``identity_only``, by
+    default ``adsp``, is the reference's ``identityOnly=self.is_adsp()``) that ``execute_values(cursor, update_sql, buffer)`` takes.  ``table``: a
     :class:`~annotatedvdb_amd.engine.VepRowsTable`, or the VEP output as a path (plain, gzip or
     bgzip) or text, with ``ranking`` (a :class:`ConsequenceRanking`, or what it takes)."""
 
-    def __init__(self, table, ranking=None, alg_id: int = 0, adsp: bool = False, engine=None):
+    def __init__(self, table, ranking=None, alg_id: int = 0, adsp: bool = False, engine=None,
+                 vep_output: bool = False, identity_only=None):
         from .engine import VepRowsTable, default_engine
         if engine is None:
             engine = table.engine if isinstance(table, VepRowsTable) else default_engine()
@@ -99,7 +123,12 @@ class VEPUpdater(object):
         if not isinstance(table, VepRowsTable):
             if ranking is None:
                 raise ValueError("a ranking is needed to build the table")
-            table = engine.vep_rows_table_build(table, ranking)
+            # identityOnly=self.is_adsp() (vep_variant_loader.py:269)
+            identity_only = bool(adsp) if identity_only is None else bool(identity_only)
+            table = engine.vep_rows_table_build(table, ranking, vep_output=vep_output, identity_only=identity_only)
+        elif vep_output and table.cleaned is None:
+            raise ValueError("the table was built without vep_output")
+        self._vep_output = table.cleaned is not None
         self._table = table
         self._alg_id, self._adsp = int(alg_id), bool(adsp)
         self._counters = {"line": table.counts["lines"], "variant": table.n_rows, "update": 0, "duplicates": 0,
@@ -117,7 +146,7 @@ class VEPUpdater(object):
         self._counters[counter] += 1
 
     def update_sql(self) -> str:
-        return update_sql(self._adsp)
+        return update_sql(self._adsp, self._vep_output)
 
     def update_buffer(self, sizeOnly=False):
         """The buffered tuples (rows from :meth:`buffer_export` are split into tuples at the first

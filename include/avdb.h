@@ -1772,6 +1772,78 @@ int avdb_vep_rows_update_write_host(const avdb_ctx* ctx, const uint8_t* text, si
                                     const uint32_t* out_len, const uint8_t* row_flags, uint8_t* out, size_t out_cap,
                                     uint64_t* row_off, uint64_t* totals);
 
+/* ---- K18c: the vep_output column of the VEP update rows ---------------------------------------
+ * xstr(cleanResult) of VEPVariantLoader.__parse_alt_alleles (vep_variant_loader.py:112-123, 202),
+ * the same text for every ALT of a line: the line's top-level object with the members
+ * colocated_variants and the four <type>_consequences removed, the value of `input` replaced by
+ * VcfEntryParser's entry dict (vcf_parser.py:76-114: chrom pos id ref alt, and qual filter info
+ * unless AVDB_VEPOUT_IDENTITY_ONLY), printed as json.dumps prints it.  On K18a's arrays of the same
+ * slab (avdb_vep_rows_in; el_rlen is not read) and K18b's entry flags (entry e is line e).
+ *   1. avdb_vep_output_size: per line its start, the length of its cleaned text, where the entry
+ *      dict begins in it and the dict's length, and a flags byte: 0, or 1 + the reason the line is
+ *      left to the caller (lengths 0): a reason of K18a or K18b (0 .. 15, as the entry's flags keep
+ *      it), 16 a kept member with a backslash escape, a byte or a token outside K18b's element
+ *      subset (reasons 13 .. 15, over the whole kept text; a byte < 0x20 anywhere in the line), 17
+ *      fewer than eight fields in `input` without AVDB_VEPOUT_IDENTITY_ONLY, 18 a field or an INFO
+ *      value outside K17's device forms (avdb_qc_table_size), a backslash other than the
+ *      separators', a byte json.dumps escapes, an INFO that to_numeric turns into a number or
+ *      that repeats a key.  counts: AVDB_VEPOUT_N_COUNTS x u64, set by the call.
+ *   2. avdb_vep_output_write (out_off: the caller's offsets; a line with flags != 0 is skipped, its
+ *      out_len bytes are the caller's to fill): the cleaned texts.  totals[0]: bytes written,
+ *      totals[1]: lines whose text differs from out_len or does not fit (nothing is written there).
+ * avdb_vep_output_update_write: avdb_vep_rows_update_write with the extra column, one wave per row:
+ *   pk<TAB>chr<label><TAB>most severe<TAB>ranked<TAB>vep_output<TAB>alg_id[<TAB>true]<LF>
+ * out_len: avdb_vep_rows_update_size's with 1 + len[row_entry[match]] added by the caller.  A row
+ * whose parts do not add up to its out_len is left blank.
+ * Workspace: avdb_vep_output_workspace_size (size, write), avdb_vep_rows_update_workspace_size
+ * (update write). */
+#define AVDB_VEPOUT_IDENTITY_ONLY 0x01u
+#define AVDB_VEPOUT_N_REASONS 19
+#define AVDB_VEPOUT_COUNT_LINES 0
+#define AVDB_VEPOUT_COUNT_HOST_LINES 1
+#define AVDB_VEPOUT_COUNT_OUT_BYTES 2
+#define AVDB_VEPOUT_COUNT_REASON0 3
+#define AVDB_VEPOUT_N_COUNTS 22
+typedef struct avdb_vep_output_table {
+  uint32_t struct_size; /* sizeof(avdb_vep_output_table) */
+  uint32_t reserved;
+  uint64_t n_entries;
+  const uint8_t* text; /* the cleaned texts */
+  uint64_t text_bytes;
+  const uint64_t* off;      /* per entry */
+  const uint32_t* len;      /* per entry */
+  const int32_t* row_entry; /* per row of the avdb_vep_rows_table */
+} avdb_vep_output_table;
+int avdb_vep_output_workspace_size(size_t text_bytes, size_t n_lines, size_t* bytes);
+int avdb_vep_output_size(avdb_ctx* ctx, const uint8_t* text, size_t text_bytes, size_t n_lines,
+                         const avdb_vep_rows_in* in, const uint8_t* ent_flags, uint32_t flags, uint64_t* line_start,
+                         uint32_t* out_len, uint32_t* dict_at, uint32_t* dict_len, uint8_t* out_flags, uint64_t* counts,
+                         void* workspace, size_t workspace_bytes, void* stream);
+int avdb_vep_output_write(avdb_ctx* ctx, const uint8_t* text, size_t text_bytes, size_t n_lines,
+                          const avdb_vep_rows_in* in, uint32_t flags, const uint64_t* out_off, const uint32_t* out_len,
+                          const uint32_t* dict_at, const uint32_t* dict_len, const uint8_t* out_flags, uint8_t* out,
+                          size_t out_cap, uint64_t* totals, void* workspace, size_t workspace_bytes, void* stream);
+int avdb_vep_output_size_host(const avdb_ctx* ctx, const uint8_t* text, size_t text_bytes, size_t n_lines,
+                              const avdb_vep_rows_in* in, const uint8_t* ent_flags, uint32_t flags,
+                              uint64_t* line_start, uint32_t* out_len, uint32_t* dict_at, uint32_t* dict_len,
+                              uint8_t* out_flags, uint64_t* counts);
+int avdb_vep_output_write_host(const avdb_ctx* ctx, const uint8_t* text, size_t text_bytes, size_t n_lines,
+                               const avdb_vep_rows_in* in, uint32_t flags, const uint64_t* out_off,
+                               const uint32_t* out_len, const uint32_t* dict_at, const uint32_t* dict_len,
+                               const uint8_t* out_flags, uint8_t* out, size_t out_cap, uint64_t* totals);
+int avdb_vep_output_update_write(avdb_ctx* ctx, const uint8_t* text, size_t text_bytes, size_t n_lines, size_t n_rows,
+                                 const avdb_vep_rows_table* table, const avdb_vep_output_table* cleaned, uint32_t flags,
+                                 uint64_t alg_id, const uint64_t* row_start, const uint32_t* pk_len,
+                                 const int32_t* match, const uint32_t* out_len, const uint8_t* row_flags, uint8_t* out,
+                                 size_t out_cap, uint64_t* row_off, uint64_t* totals, void* workspace,
+                                 size_t workspace_bytes, void* stream);
+int avdb_vep_output_update_write_host(const avdb_ctx* ctx, const uint8_t* text, size_t text_bytes, size_t n_lines,
+                                      size_t n_rows, const avdb_vep_rows_table* table,
+                                      const avdb_vep_output_table* cleaned, uint32_t flags, uint64_t alg_id,
+                                      const uint64_t* row_start, const uint32_t* pk_len, const int32_t* match,
+                                      const uint32_t* out_len, const uint8_t* row_flags, uint8_t* out, size_t out_cap,
+                                      uint64_t* row_off, uint64_t* totals);
+
 /* ---- host-side formatting of kernel outputs -------------------------------
  * ltree path text (<= AVDB_MAX_PATH bytes).  Returns the length written (no
  * NUL terminator counted; one is written if cap allows), or a negative code. */
