@@ -124,6 +124,12 @@ VEPOUT_REASONS = VEPROWS_REASONS + ("kept_text", "eight_fields",
                                     "input_value")  # why a line's cleaned text is the host's, by flags - 1
 VEPOUT_COUNTS = ("lines", "host_lines", "out_bytes") + VEPOUT_REASONS  # AVDB_VEPOUT_COUNT_*, by slot
 VEPOUT_N_COUNTS = len(VEPOUT_COUNTS)
+VEPFREQ_IDENTITY_ONLY, VEPFREQ_MATCH_REFSNP, VEPFREQ_MAX_MEMBERS = 1, 2, 64  # AVDB_VEPFREQ_*
+VEPFREQ_REASONS = VEPROWS_REASONS + ("colocated", "element_key", "repeated_key", "colocated_bytes", "not_object",
+                                     "member_value", "members", "gmaf", "info", "freq_item", "freq_number",
+                                     "same_allele")  # K18d's reasons 16 .. 27, behind K18b's
+VEPFREQ_COUNTS = ("lines", "host_lines", "rows", "out_bytes") + VEPFREQ_REASONS  # AVDB_VEPFREQ_COUNT_*, by slot
+VEPFREQ_N_COUNTS = len(VEPFREQ_COUNTS)
 EXPVCF_ROW_HOST, EXPVCF_BAD, EXPVCF_DROPPED = 1, 2, 4  # AVDB_EXPVCF_* row flags
 EXPVCF_STREAM_VCF, EXPVCF_STREAM_INVALID = 0, 1
 EXPVCF_COUNTS = ("valid", "invalid", "skipped_lines", "filtered", "bad", "lone_cr", "vcf_bytes",
@@ -250,6 +256,16 @@ class VepOutputTable(ctypes.Structure):
         super().__init__(ctypes.sizeof(VepOutputTable), 0, n_entries, text, text_bytes, off, length, row_entry)
 
 
+class VepFreqTable(ctypes.Structure):
+    """avdb_vep_freq_table (include/avdb.h); ``struct_size`` is filled in."""
+    _fields_ = [("struct_size", ctypes.c_uint32), ("reserved", ctypes.c_uint32), ("n_rows", ctypes.c_uint64),
+                ("text", ctypes.c_void_p), ("text_bytes", ctypes.c_uint64), ("off", ctypes.c_void_p),
+                ("len", ctypes.c_void_p)]
+
+    def __init__(self, n_rows: int = 0, text=None, text_bytes: int = 0, off=None, length=None):
+        super().__init__(ctypes.sizeof(VepFreqTable), 0, n_rows, text, text_bytes, off, length)
+
+
 class LineResult(ctypes.Structure):
     """avdb_line_result (include/avdb.h)."""
     _fields_ = [(name, ctypes.c_uint32) for name in ("state", "flags", "copy_bytes", "map_bytes", "n_rec", "n_rows",
@@ -315,6 +331,9 @@ EXPORTED_SYMBOLS = [
     "avdb_vep_output_workspace_size", "avdb_vep_output_size", "avdb_vep_output_write",
     "avdb_vep_output_size_host", "avdb_vep_output_write_host",
     "avdb_vep_output_update_write", "avdb_vep_output_update_write_host",
+    "avdb_vep_freq_workspace_size", "avdb_vep_freq_size", "avdb_vep_freq_write",
+    "avdb_vep_freq_size_host", "avdb_vep_freq_write_host", "avdb_vep_freq_token_ok_host",
+    "avdb_vep_freq_update_write", "avdb_vep_freq_update_write_host",
 ]
 
 
@@ -536,6 +555,16 @@ def _sig(lib):
     f.avdb_vep_output_update_write_host.argtypes = [P, P, SZ, SZ, SZ, LT, ctypes.POINTER(VepOutputTable), U32,
                                                     ctypes.c_uint64, P, P, P, P, P, P, SZ, P, P]
     f.avdb_vep_output_update_write.argtypes = f.avdb_vep_output_update_write_host.argtypes + [P, SZ, P]
+    f.avdb_vep_freq_workspace_size.argtypes = [SZ, SZ, ctypes.POINTER(SZ)]
+    f.avdb_vep_freq_size_host.argtypes = [P, P, SZ, SZ, SZ, VR, P, P, P, P, U32] + [P] * 7
+    f.avdb_vep_freq_size.argtypes = f.avdb_vep_freq_size_host.argtypes + [P, SZ, P]
+    f.avdb_vep_freq_write_host.argtypes = [P, P, SZ, SZ, SZ, VR] + [P] * 10 + [SZ, P]
+    f.avdb_vep_freq_write.argtypes = f.avdb_vep_freq_write_host.argtypes + [P, SZ, P]
+    f.avdb_vep_freq_token_ok_host.argtypes = [P, SZ]
+    f.avdb_vep_freq_update_write_host.argtypes = [P, P, SZ, SZ, SZ, LT, ctypes.POINTER(VepFreqTable),
+                                                  ctypes.POINTER(VepOutputTable), U32, ctypes.c_uint64, P, P, P, P, P,
+                                                  P, SZ, P, P]
+    f.avdb_vep_freq_update_write.argtypes = f.avdb_vep_freq_update_write_host.argtypes + [P, SZ, P]
     for name in EXPORTED_SYMBOLS:
         if name not in ("avdb_last_error",):
             getattr(f, name).restype = I32

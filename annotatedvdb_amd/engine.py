@@ -195,7 +195,11 @@ class VepRowsTable(LofTable):
     ``cleaned[cleaned_off[e]:cleaned_off[e] + cleaned_len[e]]``, ``row_entry[k]`` the entry of row
     ``k`` (the rows of a multi-allelic line share one text), ``cleaned_flags[e]`` 0 or 1 + the reason
     the host rendered it (``N.VEPOUT_REASONS``), ``cleaned_counts`` by ``N.VEPOUT_COUNTS``,
-    ``identity_only`` the form of ``input``'s dict; else these are ``None``."""
+    ``identity_only`` the form of ``input``'s dict; else these are ``None``.  Built with
+    ``allele_frequencies=True`` (K18d) it holds every row's ``allele_frequencies`` text, one per ALT allele:
+    row ``k``'s is ``freq[freq_off[k]:freq_off[k] + freq_len[k]]``, ``freq_flags[e]`` 0 or 1 + the reason the
+    host rendered line ``e``'s (``N.VEPFREQ_REASONS``), ``freq_counts`` by ``N.VEPFREQ_COUNTS``,
+    ``match_refsnp`` whether the element was matched by ``ref_snp_id``; else these are ``None``."""
     ranking: object = None
     unranked: list = None
     _keep: tuple = ()  # K18a's arrays and the rank text, which the table's build read
@@ -206,6 +210,17 @@ class VepRowsTable(LofTable):
     cleaned_flags: torch.Tensor = None
     cleaned_counts: Dict[str, int] = None
     identity_only: bool = False
+    freq: torch.Tensor = None
+    freq_off: torch.Tensor = None
+    freq_len: torch.Tensor = None
+    freq_flags: torch.Tensor = None
+    freq_counts: Dict[str, int] = None
+    match_refsnp: bool = False
+
+    def freq_view(self) -> "N.VepFreqTable":
+        """The C struct over the frequency texts (valid while the tensors are alive)."""
+        return N.VepFreqTable(self.n_rows, N.ptr(self.freq), self.freq.numel(), N.ptr(self.freq_off),
+                              N.ptr(self.freq_len))
 
     def cleaned_view(self) -> "N.VepOutputTable":
         """The C struct over the cleaned texts (valid while the tensors are alive)."""
@@ -1710,8 +1725,8 @@ class Engine:
         return slab_passes.vep_consequences(self, text, ranking)
 
     # -- K18b: VEP consequence update rows ------------------------------------------------
-    def vep_rows_table_build(self, text, ranking, vep_output: bool = False,
-                             identity_only: bool = False) -> "VepRowsTable":
+    def vep_rows_table_build(self, text, ranking, vep_output: bool = False, identity_only: bool = False,
+                             allele_frequencies: bool = False, match_refsnp: bool = False) -> "VepRowsTable":
         """K18b: VEP ``--json`` output (what :meth:`vep_consequences` takes) and a ranking ->
         :class:`VepRowsTable` on this engine's device: K18a's pass, then one row per ALT allele of the
         VCF line in every line's ``input``, keyed by its metaseq id ``chrom:pos:ref:alt``, its body what
@@ -1731,8 +1746,19 @@ class Engine:
         ``VcfEntryParser(input, identityOnly=identity_only).get_entry()`` in place of ``input``.  A
         line outside that pass's device subset (``cleaned_counts``) is rendered by
         :func:`annotatedvdb_amd.vep_rows.vep_output_line`.  With ``vep_output=False`` the table is
-        K18b's, byte for byte."""
-        return slab_passes.vep_rows_table_build(self, text, ranking, vep_output, identity_only)
+        K18b's, byte for byte.
+
+        ``allele_frequencies=True`` (K18d) adds every row's ``allele_frequencies`` text:
+        ``xstr(alleleFreq, nullStr='{}')`` of ``__parse_alt_alleles`` (``vep_variant_loader.py:85-109,
+        126-142, 190-199``): the frequencies of the normalised ALT in the element of
+        ``colocated_variants`` that ``VepJsonParser.get_frequencies`` takes (matched by ``ref_snp_id``
+        with ``match_refsnp``, the reference's dbSNP datasource), regrouped by source, with the ALT's
+        column of INFO ``FREQ`` merged in (not with ``identity_only``).  A line outside that pass's
+        device subset (``freq_counts``) is rendered by
+        :func:`annotatedvdb_amd.vep_rows.allele_frequencies_line`.  Without it the table is what it
+        was, byte for byte."""
+        return slab_passes.vep_rows_table_build(self, text, ranking, vep_output, identity_only, allele_frequencies,
+                                                match_refsnp)
 
     def vep_update_rows(self, text, table: "VepRowsTable", alg_id: int, adsp: bool = False,
                         update_existing: bool = False, contigs=None) -> "LofUpdateRows":
@@ -1744,7 +1770,9 @@ class Engine:
         (``has_attribute('vep_output', ...)`` with ``skip_existing``); an id the table lacks is
         counted ``not_annotated``; ``table.hit`` records the table rows matched.  A table built with
         ``vep_output=True`` (K18c) gives ``...<TAB>ranked<TAB>vep_output<TAB>alg_id...`` rows, written
-        one wave per row."""
+        one wave per row; one built with ``allele_frequencies=True`` (K18d) gives
+        ``pk<TAB>chr<label><TAB>allele_frequencies<TAB>most severe<TAB>ranked[<TAB>vep_output]<TAB>alg_id...``
+        rows, ``updateValues``' order, written the same way."""
         return slab_passes.vep_update_rows(self, text, table, alg_id, adsp, update_existing, contigs)
 
     # -- K17: ADSP QC pVCF update rows --------------------------------------------------

@@ -1,18 +1,21 @@
 """``adsp_most_severe_consequence`` / ``adsp_ranked_consequences`` update rows from VEP's JSON output —
 the counterpart of ``Load/bin/load_vep_result.py`` for these two columns (K18b) and, with ``--vepOutput``,
-for ``vep_output`` (K18c; ``allele_frequencies`` is K18d), with an export of ``AnnotatedVDB.Variant`` in place of the database
+for ``vep_output`` (K18c) and with ``--alleleFrequencies`` for ``allele_frequencies`` (K18d), with an export of ``AnnotatedVDB.Variant`` in place of the database
 (:mod:`annotatedvdb_amd.vep_rows`).
 
     python -m annotatedvdb_amd.load_vep_result --fileName chr1.vep.json.gz --rankingFile ranking.txt \\
         --export variant_export.tsv.gz --outFile vep_rows.tsv --algInvocationId 42 [--datasource ADSP] \\
-        [--updateExisting] [--existingContigs 1,2] [--skipMissing] [--vepOutput]
+        [--updateExisting] [--existingContigs 1,2] [--skipMissing] [--vepOutput] [--alleleFrequencies]
 
 ``--fileName``, ``--rankingFile``, ``--updateExisting`` and ``--datasource`` are the reference's.
 ``--export`` is ``COPY (SELECT record_primary_key, metaseq_id, vep_output FROM AnnotatedVDB.Variant)
 TO ...`` (plain, gzip or bgzip); ``--existingContigs`` keeps only the export rows of these
-chromosomes.  ``--outFile`` receives the rows ``record_primary_key<TAB>chromosome<TAB>most
+chromosomes.  ``--outFile`` receives the rows ``record_primary_key<TAB>chromosome[<TAB>allele_frequencies]<TAB>most
 severe<TAB>ranked[<TAB>vep_output]<TAB>row_algorithm_id[<TAB>true]`` (``vep_output``, the cleaned result, with
-``--vepOutput``; its ``input`` has the five identity fields for ``--datasource ADSP``, else all eight) that ``execute_values(cursor, update_sql, ...)``
+``--vepOutput``; its ``input`` has the five identity fields for ``--datasource ADSP``, else all eight;
+``allele_frequencies`` with ``--alleleFrequencies``: the element of ``colocated_variants`` is matched by the
+variant's refSNP id for ``--datasource dbSNP``, and INFO ``FREQ`` is merged in unless the datasource is ADSP;
+with both switches the rows are the reference's full ``updateValues`` and the statement its full one) that ``execute_values(cursor, update_sql, ...)``
 takes as tuples, ``<outFile>.update.sql`` the statement, ``<outFile>.unranked`` the lines that need a
 re-rank (``line<TAB>id<TAB>combination``; the run then ends with exit code 2).  A variant of the
 file no export row matches ends the run, before anything is written, with the reference's
@@ -40,6 +43,8 @@ def parse_args(argv: Optional[Sequence[str]] = None):
     ap.add_argument("--existingContigs", help="comma separated chromosomes whose export rows to keep")
     ap.add_argument("--skipMissing", action="store_true", help="go on when a variant of the file is not in the export")
     ap.add_argument("--vepOutput", action="store_true", help="add the vep_output column (the cleaned result)")
+    ap.add_argument("--alleleFrequencies", action="store_true",
+                    help="add the allele_frequencies column (colocated_variants frequencies and INFO FREQ)")
     ap.add_argument("--device", default=None, help="GPU index, or 'host'")
     return ap.parse_args(argv)
 
@@ -52,7 +57,8 @@ def main(argv: Optional[Sequence[str]] = None, engine=None) -> int:
         engine = Engine(args.device if args.device in (None, "host") else int(args.device))
     from .vep_rows import VEPUpdater
     updater = VEPUpdater(args.fileName, args.rankingFile, alg_id=args.algInvocationId,
-                         adsp=args.datasource.lower() == "adsp", engine=engine, vep_output=args.vepOutput)
+                         adsp=args.datasource.lower() == "adsp", engine=engine, vep_output=args.vepOutput,
+                         allele_frequencies=args.alleleFrequencies, dbsnp=args.datasource.lower() == "dbsnp")
     contigs = [c.replace("chr", "") for c in args.existingContigs.split(",")] if args.existingContigs else None
     updater.buffer_export(args.export, update_existing=args.updateExisting, contigs=contigs)
     missing = updater.unmatched()

@@ -2,7 +2,7 @@
 K10a ``cadd_table_build``, K12 ``existing_table_build``, K13 ``cadd_update_rows``, K14
 ``export_vcf``, K15 ``split_vcf``, K16 ``lof_table_build`` / ``lof_update_rows``, K17
 ``qc_table_build`` / ``qc_update_rows``, K18a ``vep_consequences``, K18b ``vep_rows_table_build`` /
-``vep_update_rows`` (with K18c's ``vep_output`` column on request) and K19 ``txt_table_build`` /
+``vep_update_rows`` (with K18c's ``vep_output`` and K18d's ``allele_frequencies`` columns on request) and K19 ``txt_table_build`` /
 ``txt_update_rows`` / ``txt_direct_rows``.
 
 The two-pass ones have one shape: line count -> size pass -> its counts to the host (second
@@ -615,7 +615,71 @@ def _vep_cleaned(engine, text, view, ent_flags, row_line_start, identity_only: b
     return blob[:total], off[:nl], out_len[:nl], row_entry, flags[:nl], cnt
 
 
-def vep_rows_table_build(engine, text, ranking, vep_output: bool = False, identity_only: bool = False):
+def _vep_freq(engine, text, view, ents, n_rows: int, identity_only: bool, match_refsnp: bool):
+    """K18d: the ``allele_frequencies`` text of every row of the table K18b built from the slab: the size pass,
+    the lines it leaves to the host rendered by :func:`~annotatedvdb_amd.vep_rows.allele_frequencies_line`, the
+    offsets, the write pass, the host texts copied into their rows' spans.  ``view``: K18b's ``VepRowsIn``;
+    ``ents``: its entries' columns (entry e is line e).  Returns ``(blob, off, len, flags, counts)``."""
+    from .vep_rows import allele_frequencies_line
+    sp = SlabPass(engine, text, "vep_freq", "avdb_vep_freq_workspace_size")
+    nl = sp.n_lines
+    ent_start, ent_alts, _, _, ent_flags = ents
+    alts = ent_alts[:nl].long()
+    row0 = torch.zeros(sp.m, dtype=torch.int64, device=engine.device)
+    row0[:nl] = torch.cumsum(alts, 0) - alts
+    fr_start, fr_len, fq_start, fq_len, flags = sp.cols(torch.int64, torch.int32, torch.int64, torch.int32, torch.uint8)
+    freq_len = torch.zeros(max(1, n_rows), dtype=torch.int32, device=engine.device)
+    counts = engine.empty(N.VEPFREQ_N_COUNTS, torch.int64)
+    fl = (N.VEPFREQ_IDENTITY_ONLY if identity_only else 0) | (N.VEPFREQ_MATCH_REFSNP if match_refsnp else 0)
+    vp = ctypes.byref(view)
+    sp.call("avdb_vep_freq_size", sp.tp, sp.nb, nl, n_rows, vp, ent_start, ent_alts, ent_flags, row0, fl, fr_start, fr_len,
+            fq_start, fq_len, flags, freq_len, counts)
+    cnt = sp.counts(counts, N.VEPFREQ_COUNTS)
+    device_bytes = cnt["out_bytes"]
+    rows_at, rendered = [], []
+    if cnt["host_lines"]:
+        host = torch.nonzero(flags[:nl]).flatten()
+        for at, first, n, b in zip(ent_start[host].tolist(), row0[host].tolist(), alts[host].tolist(),
+                                   sp.rows_bytes(ent_start[host], _lines_to_next(sp, host, ent_start, nl))):
+            if n == 0:  # (a line K18b lists as unranked: it has no rows)
+                continue
+            try:
+                texts = [t.encode("utf-8") for _, t in allele_frequencies_line(b.split(b"\n", 1)[0], identity_only,
+                                                                              match_refsnp)]
+                if len(texts) != n:
+                    raise ValueError(f"{len(texts)} ALT alleles where the table has {n} rows")
+            except Exception as err:
+                err.line = _line_number(sp, at)
+                err.counts = cnt  # (the size pass's counts by reason: what sent the line here)
+                if hasattr(err, "add_note"):
+                    err.add_note(f"line {err.line} of the VEP output")
+                raise
+            rows_at += range(first, first + n)
+            rendered += texts
+        if rows_at:
+            rows_at = torch.tensor(rows_at, dtype=torch.int64).to(engine.device)
+            freq_len[rows_at] = sp.lengths(rendered).to(torch.int32)
+            cnt["rows"] += len(rendered)
+            cnt["out_bytes"] += sum(map(len, rendered))
+    total = cnt["out_bytes"]
+    lens = freq_len[:n_rows].long()
+    off = torch.zeros(max(1, n_rows), dtype=torch.int64, device=engine.device)
+    off[:n_rows] = torch.cumsum(lens, 0) - lens
+    blob = engine.empty(max(1, total), torch.uint8)
+    totals = engine.empty(2, torch.int64)
+    sp.call("avdb_vep_freq_write", sp.tp, sp.nb, nl, n_rows, vp, ent_alts, row0, fr_start, fr_len, fq_start, fq_len, flags,
+            off, freq_len, blob, total, totals)
+    if len(rendered):
+        sp.splice(blob, off[rows_at], rendered)
+    got = totals.cpu().tolist()
+    if got != [device_bytes, 0]:
+        raise N.NativeError("avdb_vep_freq_write" + sp.suffix, N.AVDB_ERANGE,
+                            f"{got[0]} bytes written, {got[1]} row(s) that differ from the size pass's {device_bytes} bytes")
+    return blob[:total], off[:n_rows], freq_len[:n_rows], flags[:nl], cnt
+
+
+def vep_rows_table_build(engine, text, ranking, vep_output: bool = False, identity_only: bool = False,
+                         allele_frequencies: bool = False, match_refsnp: bool = False):
     import json
     import os
     from . import bgzf
@@ -654,7 +718,7 @@ def vep_rows_table_build(engine, text, ranking, vep_output: bool = False, identi
         return ([k.encode("utf-8") for k, _, _ in rows],
                 [(ms + "\t" + ranked).encode("utf-8") for _, ms, ranked in rows], 0)
 
-    kept = {} if vep_output else None
+    kept = {} if vep_output or allele_frequencies else None
     parts = _alt_table_build(engine, text, "vep_rows_table", N.VEPROWS_COUNTS, (ctypes.byref(view),), host_line,
                              what="VEP output", row_json=True, keep=kept)
     table = E.VepRowsTable(*parts, ranking, unranked, (csq, blob, rank_off, el_rlen))
@@ -662,6 +726,10 @@ def vep_rows_table_build(engine, text, ranking, vep_output: bool = False, identi
         (table.cleaned, table.cleaned_off, table.cleaned_len, table.row_entry, table.cleaned_flags,
          table.cleaned_counts) = _vep_cleaned(engine, text, view, kept["ents"][4], table.line_start, identity_only)
         table.identity_only = bool(identity_only)
+    if allele_frequencies:
+        (table.freq, table.freq_off, table.freq_len, table.freq_flags, table.freq_counts) = _vep_freq(
+            engine, text, view, kept["ents"], table.n_rows, identity_only, match_refsnp)
+        table.identity_only, table.match_refsnp = bool(identity_only), bool(match_refsnp)
     return table
 
 
@@ -674,14 +742,23 @@ def vep_update_rows(engine, text, table, alg_id: int, adsp: bool = False, update
     flags = (N.VEPUPD_UPDATE_EXISTING if update_existing else 0) | (N.VEPUPD_ADSP if adsp else 0)
     widen = write_name = None
     write_extra = (flags, alg_id)
-    if table.cleaned is not None:  # K18c: the row grows by <TAB> and its line's cleaned text
-        cleaned = table.cleaned_view()
+    cleaned = table.cleaned_view() if table.cleaned is not None else None
+    if table.freq is not None:  # K18d: the row grows by its own frequency text and <TAB> (and K18c's part)
+        freq = table.freq_view()
+        write_name = "avdb_vep_freq_update_write"
+        write_extra = (ctypes.byref(freq), ctypes.byref(cleaned) if cleaned is not None else None, flags, alg_id)
+    elif cleaned is not None:  # K18c: the row grows by <TAB> and its line's cleaned text
         write_name, write_extra = "avdb_vep_output_update_write", (ctypes.byref(cleaned), flags, alg_id)
-
+    if write_name is not None:
         def widen(sp, row_start, out_len, row_flags, match, n, cnt):
             if n:
-                add = 1 + table.cleaned_len[table.row_entry[match[:n].long()].long()]
-                out_len[:n] += add
+                rows = match[:n].long()
+                add = torch.zeros(n, dtype=torch.int64, device=engine.device)
+                if cleaned is not None:
+                    add += 1 + table.cleaned_len[table.row_entry[rows].long()]
+                if table.freq is not None:
+                    add += 1 + table.freq_len[rows]
+                out_len[:n] += add.to(out_len.dtype)
                 cnt["out_bytes"] += int(add.sum())
 
     n, out, row_off, match, _, cnt = _table_update_rows(

@@ -1,8 +1,8 @@
 """K18b: VEP results -> ``adsp_most_severe_consequence`` / ``adsp_ranked_consequences`` update rows,
 without a database — two of the four JSON columns of ``Load/bin/load_vep_result.py`` on
 ``VEPVariantLoader`` (``vep_variant_loader.py:153-213``), and on request a third, ``vep_output`` (K18c:
-the cleaned result, :func:`vep_output_line`).  ``allele_frequencies`` is not rendered here (K18d,
-DESIGN.md §7).
+the cleaned result, :func:`vep_output_line`) and the fourth, ``allele_frequencies`` (K18d:
+:func:`allele_frequencies_line`).
 
 The reference walks VEP's ``--json`` output on one host thread: per line a ``json.loads``, a
 ``VcfEntryParser`` of the top-level ``input`` string, the consequences ranked and sorted (K18a), and
@@ -87,16 +87,91 @@ def vep_output_line(line, identity_only: bool = False) -> str:
     return json.dumps(annotation)
 
 
-def update_sql(adsp: bool = False, vep_output: bool = False) -> str:
+def _deep_update(a: dict, b: dict) -> dict:
+    """``deep_update`` as DESIGN.md (K18d) takes it: the recursive in-place merge, new keys appended."""
+    for key, value in b.items():
+        if isinstance(value, dict) and isinstance(a.get(key), dict):
+            _deep_update(a[key], value)
+        else:
+            a[key] = value
+    return a
+
+
+def _group_frequencies_by_source(frequencies):
+    """``VepJsonParser.__group_frequencies_by_source`` (``vep_parser.py:235-254``)."""
+    if frequencies is None:
+        return None
+    result = {}
+    for allele in frequencies:
+        items = frequencies[allele].items()
+        gnomad = {k: v for k, v in items if "gnomad" in k}
+        esp = {k: v for k, v in items if k in ("aa", "ea")}
+        genomes = {k: v for k, v in items if "gnomad" not in k and k not in ("aa", "ea")}
+        for name, group in (("GnomAD", gnomad), ("1000Genomes", genomes), ("ESP", esp)):
+            if group:
+                result.setdefault(allele, {})[name] = group
+    return result
+
+
+def result_frequencies(annotation: dict, matching_variant_id=None):
+    """``VepJsonParser.get_frequencies(matchingVariantId)['values']`` (``vep_parser.py:178-232``) of a parsed
+    line, or ``None``."""
+    if "colocated_variants" not in annotation:
+        return None
+    cv = annotation["colocated_variants"]
+    chosen, found = None, False
+    if len(cv) > 1:
+        for covar in cv:
+            if covar["allele_string"] != "COSMIC_MUTATION" and "frequencies" in covar:
+                if matching_variant_id is None or covar["id"] == matching_variant_id:
+                    chosen, found = covar, True
+    elif "frequencies" in cv[0]:
+        chosen, found = cv[0], True
+    return _group_frequencies_by_source(chosen["frequencies"]) if found else None
+
+
+def allele_frequencies_line(line, identity_only: bool = False, match_refsnp: bool = False) -> List[Tuple[str, str]]:
+    """K18d's host path: ``[(metaseq id, xstr(alleleFreq, nullStr='{}'))]``, one per ALT allele of ``input``, of one
+    line (``bytes`` or ``str``) as ``__parse_alt_alleles`` (``vep_variant_loader.py:153-199``) makes them: the
+    frequencies of the normalised ALT in the element ``get_frequencies`` takes (``match_refsnp``: the one whose
+    ``id`` is the variant's ``ref_snp_id``, the reference's dbSNP datasource), regrouped by source, and
+    ``VcfEntryParser.get_frequencies(alt)`` (INFO ``FREQ``; none with ``identity_only``) merged into them in place,
+    so that two ALTs with one normalised allele see each other's ``gmaf`` as they do there.  Raises what the
+    reference raises: ``json.JSONDecodeError``, ``KeyError`` (``input``, ``allele_string``, ``id``), ``IndexError``
+    (an empty ``colocated_variants``, fewer fields, fewer ``FREQ`` items than ALTs), ``AttributeError`` /
+    ``TypeError`` (values that are not the containers or strings it expects), ``ImportError``."""
+    annotation = json.loads(line)
+    entry = VcfEntryParser(annotation["input"], identityOnly=identity_only)
+    variant = entry.get_variant(dbSNP=match_refsnp, namespace=True)
+    frequencies = result_frequencies(annotation, variant.ref_snp_id if match_refsnp else None)
+    rows = []
+    for alt in variant.alt_alleles:
+        annotator = VariantAnnotator(variant.ref_allele, alt, variant.chromosome, variant.position)
+        _, norm_alt = annotator.get_normalized_alleles(snvDivMinus=True)
+        allele_freq = frequencies[norm_alt] if frequencies is not None and norm_alt in frequencies else None
+        gmafs = entry.get_frequencies(alt)
+        if allele_freq is None:
+            allele_freq = gmafs
+        elif gmafs is not None:
+            allele_freq = _deep_update(allele_freq, gmafs)
+        rows.append((annotator.get_metaseq_id(), _xstr_json(allele_freq)))
+    return rows
+
+
+def update_sql(adsp: bool = False, vep_output: bool = False, allele_frequencies: bool = False) -> str:
     """``initialize_update_sql`` (``vep_variant_loader.py:215-247``) over this pass's fields;
-    ``vep_output``: the cleaned result's column too, before ``row_algorithm_id`` as in ``COPY_FIELDS``."""
+    ``vep_output``: the cleaned result's column too, before ``row_algorithm_id`` as in ``COPY_FIELDS``;
+    ``allele_frequencies``: that column too, first behind the keys as there.  With both the statement is
+    the reference's."""
     fields = list(UPDATE_FIELDS)
     if vep_output:
         fields.insert(fields.index("row_algorithm_id"), "vep_output")
+    if allele_frequencies:
+        fields.insert(0, "allele_frequencies")
     fields += ["is_adsp_variant"] if adsp else []
     sets = []
     for f in fields:
-        if f in JSONB_UPDATE_FIELDS or f == "vep_output":
+        if f in JSONB_UPDATE_FIELDS or f in ("vep_output", "allele_frequencies"):
             sets.append(f"{f} = jsonb_merge(COALESCE(v.{f} ,'{{}}'::jsonb), d.{f}::jsonb)")
         else:
             sets.append(f"{f} = d.{f}")
@@ -108,14 +183,16 @@ def update_sql(adsp: bool = False, vep_output: bool = False) -> str:
 class VEPUpdater(object):
     """The reference loader's observable surface for the two consequence columns, batch-wise and
     without a database, in the mould of :class:`~annotatedvdb_amd.snpeff_lof.LOFUpdater`: counters
-    and the update buffer of ``(record_primary_key, 'chr' + c, most severe, ranked[, vep_output], alg id[,
-    'true'])`` tuples (``vep_output``: K18c's column, the table built with it; ``identity_only``, by
+    and the update buffer of ``(record_primary_key, 'chr' + c[, allele_frequencies], most severe, ranked[,
+    vep_output], alg id[, 'true'])`` tuples (``vep_output``: K18c's column, ``allele_frequencies``: K18d's, the
+    table built with them; ``dbsnp``: the reference's ``is_dbsnp()``, the element is matched by ``ref_snp_id``;
+    ``identity_only``, by
     default ``adsp``, is the reference's ``identityOnly=self.is_adsp()``) that ``execute_values(cursor, update_sql, buffer)`` takes.  ``table``: a
     :class:`~annotatedvdb_amd.engine.VepRowsTable`, or the VEP output as a path (plain, gzip or
     bgzip) or text, with ``ranking`` (a :class:`ConsequenceRanking`, or what it takes)."""
 
     def __init__(self, table, ranking=None, alg_id: int = 0, adsp: bool = False, engine=None,
-                 vep_output: bool = False, identity_only=None):
+                 vep_output: bool = False, identity_only=None, allele_frequencies: bool = False, dbsnp: bool = False):
         from .engine import VepRowsTable, default_engine
         if engine is None:
             engine = table.engine if isinstance(table, VepRowsTable) else default_engine()
@@ -125,10 +202,14 @@ class VEPUpdater(object):
                 raise ValueError("a ranking is needed to build the table")
             # identityOnly=self.is_adsp() (vep_variant_loader.py:269)
             identity_only = bool(adsp) if identity_only is None else bool(identity_only)
-            table = engine.vep_rows_table_build(table, ranking, vep_output=vep_output, identity_only=identity_only)
+            table = engine.vep_rows_table_build(table, ranking, vep_output=vep_output, identity_only=identity_only,
+                                                allele_frequencies=allele_frequencies, match_refsnp=bool(dbsnp))
         elif vep_output and table.cleaned is None:
             raise ValueError("the table was built without vep_output")
+        elif allele_frequencies and table.freq is None:
+            raise ValueError("the table was built without allele_frequencies")
         self._vep_output = table.cleaned is not None
+        self._allele_frequencies = table.freq is not None
         self._table = table
         self._alg_id, self._adsp = int(alg_id), bool(adsp)
         self._counters = {"line": table.counts["lines"], "variant": table.n_rows, "update": 0, "duplicates": 0,
@@ -146,7 +227,7 @@ class VEPUpdater(object):
         self._counters[counter] += 1
 
     def update_sql(self) -> str:
-        return update_sql(self._adsp, self._vep_output)
+        return update_sql(self._adsp, self._vep_output, self._allele_frequencies)
 
     def update_buffer(self, sizeOnly=False):
         """The buffered tuples (rows from :meth:`buffer_export` are split into tuples at the first

@@ -1844,6 +1844,102 @@ int avdb_vep_output_update_write_host(const avdb_ctx* ctx, const uint8_t* text, 
                                       const uint32_t* out_len, const uint8_t* row_flags, uint8_t* out, size_t out_cap,
                                       uint64_t* row_off, uint64_t* totals);
 
+/* ---- K18d: the allele_frequencies column of the VEP update rows --------------------------------
+ * xstr(alleleFreq, nullStr='{}') of VEPVariantLoader.__parse_alt_alleles (vep_variant_loader.py:
+ * 85-109, 126-142, 190-199), one text per ALT allele: VepJsonParser.get_frequencies' choice among
+ * the elements of colocated_variants (one element: cv[0] when it has `frequencies`; more: the last
+ * one whose allele_string is not COSMIC_MUTATION, that has `frequencies` and, with
+ * AVDB_VEPFREQ_MATCH_REFSNP and a ref_snp_id in `input`, whose id is that), its `frequencies` of
+ * the normalised ALT regrouped as {"GnomAD": {keys that hold gnomad}, "1000Genomes": {the others},
+ * "ESP": {aa, ea}} (empty groups left out, members in source order), and the ALT's column of INFO
+ * FREQ (not with AVDB_VEPFREQ_IDENTITY_ONLY) merged in: {"gmaf": x} inside the group a population
+ * names, a new "pop": {"gmaf": x} behind the groups otherwise; '{}' when nothing is left.  On
+ * K18a's arrays of the same slab (avdb_vep_rows_in; el_rlen is not read) and K18b's entries
+ * (entry e is line e: ent_start its start, ent_alts its rows, row0 the sums of ent_alts before it).
+ *   1. avdb_vep_freq_size: per line the span of the chosen `frequencies` object (fr_len 0: none),
+ *      the span of FREQ's value (fq_len 0: none) and a flags byte: 0, or 1 + the reason the line is
+ *      left to the caller; per table row the length of its text (0 for such a line).  Reasons: one
+ *      of K18a or K18b (0 .. 15), 16 colocated_variants is no array, is empty or holds what is no
+ *      object, 17 among several elements one without allele_string, or without id where one is
+ *      matched, or either not a string, 18 a key of interest twice (colocated_variants; an element's
+ *      allele_string, id, frequencies; the allele's key; a member's key), 19 a backslash or a byte
+ *      outside printable ASCII inside colocated_variants, 20 `frequencies` or the allele's value is
+ *      no object, 21 a member's value outside the token rule (avdb_vep_freq_token_ok_host), 22 more
+ *      than AVDB_VEPFREQ_MAX_MEMBERS members, 23 a member named gmaf in a group FREQ names too, 24
+ *      fewer than eight fields in `input`, a backslash other than the separators' or a byte < 0x20
+ *      in them, an INFO to_numeric turns into a number, an RS to match that is not plain digits
+ *      without a leading zero, 25 a FREQ avdb_vcf_format leaves to the host (no ':', more than 64
+ *      or repeated populations, a name json.dumps escapes), a bare FREQ, '#' in its value, 26 a
+ *      FREQ number that is not digits with at most one '.' and 15 significant digits, or fewer
+ *      comma items than ALTs, 27 two ALTs with one normalised allele.  counts:
+ *      AVDB_VEPFREQ_N_COUNTS x u64, set by the call.
+ *   2. avdb_vep_freq_write (freq_off: the caller's offsets per row; a line with flags != 0 is
+ *      skipped, its rows' bytes are the caller's to fill): the texts.  totals[0]: bytes written,
+ *      totals[1]: rows whose text differs from freq_len or does not fit (nothing is written there).
+ * avdb_vep_freq_update_write: avdb_vep_output_update_write with the column, one wave per row:
+ *   pk<TAB>chr<label><TAB>allele_frequencies<TAB>most severe<TAB>ranked[<TAB>vep_output]<TAB>alg_id[<TAB>true]<LF>
+ * cleaned: NULL for rows without vep_output.  out_len: avdb_vep_rows_update_size's with
+ * 1 + len[match] (and 1 + the cleaned length) added by the caller.
+ * Workspace: avdb_vep_freq_workspace_size (size), avdb_vep_rows_update_workspace_size (update write). */
+#define AVDB_VEPFREQ_IDENTITY_ONLY 0x01u
+#define AVDB_VEPFREQ_MATCH_REFSNP 0x02u
+#define AVDB_VEPFREQ_MAX_MEMBERS 64
+#define AVDB_VEPFREQ_N_REASONS 28
+#define AVDB_VEPFREQ_COUNT_LINES 0
+#define AVDB_VEPFREQ_COUNT_HOST_LINES 1
+#define AVDB_VEPFREQ_COUNT_ROWS 2
+#define AVDB_VEPFREQ_COUNT_OUT_BYTES 3
+#define AVDB_VEPFREQ_COUNT_REASON0 4
+#define AVDB_VEPFREQ_N_COUNTS 32
+typedef struct avdb_vep_freq_table {
+  uint32_t struct_size; /* sizeof(avdb_vep_freq_table) */
+  uint32_t reserved;
+  uint64_t n_rows;     /* the rows of the avdb_vep_rows_table */
+  const uint8_t* text; /* the frequency texts */
+  uint64_t text_bytes;
+  const uint64_t* off; /* per row */
+  const uint32_t* len; /* per row */
+} avdb_vep_freq_table;
+int avdb_vep_freq_workspace_size(size_t text_bytes, size_t n_lines, size_t* bytes);
+int avdb_vep_freq_size(avdb_ctx* ctx, const uint8_t* text, size_t text_bytes, size_t n_lines, size_t n_rows,
+                       const avdb_vep_rows_in* in, const uint64_t* ent_start, const uint32_t* ent_alts,
+                       const uint8_t* ent_flags, const uint64_t* row0, uint32_t flags, uint64_t* fr_start,
+                       uint32_t* fr_len, uint64_t* fq_start, uint32_t* fq_len, uint8_t* out_flags, uint32_t* freq_len,
+                       uint64_t* counts, void* workspace, size_t workspace_bytes, void* stream);
+int avdb_vep_freq_write(avdb_ctx* ctx, const uint8_t* text, size_t text_bytes, size_t n_lines, size_t n_rows,
+                        const avdb_vep_rows_in* in, const uint32_t* ent_alts, const uint64_t* row0,
+                        const uint64_t* fr_start, const uint32_t* fr_len, const uint64_t* fq_start,
+                        const uint32_t* fq_len, const uint8_t* out_flags, const uint64_t* freq_off,
+                        const uint32_t* freq_len, uint8_t* out, size_t out_cap, uint64_t* totals, void* workspace,
+                        size_t workspace_bytes, void* stream);
+int avdb_vep_freq_size_host(const avdb_ctx* ctx, const uint8_t* text, size_t text_bytes, size_t n_lines, size_t n_rows,
+                            const avdb_vep_rows_in* in, const uint64_t* ent_start, const uint32_t* ent_alts,
+                            const uint8_t* ent_flags, const uint64_t* row0, uint32_t flags, uint64_t* fr_start,
+                            uint32_t* fr_len, uint64_t* fq_start, uint32_t* fq_len, uint8_t* out_flags,
+                            uint32_t* freq_len, uint64_t* counts);
+int avdb_vep_freq_write_host(const avdb_ctx* ctx, const uint8_t* text, size_t text_bytes, size_t n_lines, size_t n_rows,
+                             const avdb_vep_rows_in* in, const uint32_t* ent_alts, const uint64_t* row0,
+                             const uint64_t* fr_start, const uint32_t* fr_len, const uint64_t* fq_start,
+                             const uint32_t* fq_len, const uint8_t* out_flags, const uint64_t* freq_off,
+                             const uint32_t* freq_len, uint8_t* out, size_t out_cap, uint64_t* totals);
+/* 1 when the n bytes are a value the device copies (reason 21's rule: avdb_vep_rows_token_ok_host's, or
+ * D[.F]e-XX: D in 1 .. 9, F without a trailing zero, at most 15 significant digits, XX of two digits, or
+ * three without a leading zero, its value in 5 .. 300), else 0 */
+int avdb_vep_freq_token_ok_host(const uint8_t* token, size_t n);
+int avdb_vep_freq_update_write(avdb_ctx* ctx, const uint8_t* text, size_t text_bytes, size_t n_lines, size_t n_rows,
+                               const avdb_vep_rows_table* table, const avdb_vep_freq_table* freq,
+                               const avdb_vep_output_table* cleaned, uint32_t flags, uint64_t alg_id,
+                               const uint64_t* row_start, const uint32_t* pk_len, const int32_t* match,
+                               const uint32_t* out_len, const uint8_t* row_flags, uint8_t* out, size_t out_cap,
+                               uint64_t* row_off, uint64_t* totals, void* workspace, size_t workspace_bytes,
+                               void* stream);
+int avdb_vep_freq_update_write_host(const avdb_ctx* ctx, const uint8_t* text, size_t text_bytes, size_t n_lines,
+                                    size_t n_rows, const avdb_vep_rows_table* table, const avdb_vep_freq_table* freq,
+                                    const avdb_vep_output_table* cleaned, uint32_t flags, uint64_t alg_id,
+                                    const uint64_t* row_start, const uint32_t* pk_len, const int32_t* match,
+                                    const uint32_t* out_len, const uint8_t* row_flags, uint8_t* out, size_t out_cap,
+                                    uint64_t* row_off, uint64_t* totals);
+
 /* ---- host-side formatting of kernel outputs -------------------------------
  * ltree path text (<= AVDB_MAX_PATH bytes).  Returns the length written (no
  * NUL terminator counted; one is written if cap allows), or a negative code. */
